@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """Headline benchmark: Jaccard-evaluated read pairs / s on the 1M-read interval cluster.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one process per GPU, RCCL)
+
+A plain run does what the headline needs: it sets up, counts the input's Jaccard-evaluated pairs
+(one walk-engine query), warms up, times K full-work steps, writes the last step's outputs when
+``--dump-outputs DIR`` is given and prints the result line (``value``, ``ms_per_step`` and the
+``roofline`` of the timed launches).  ``--full`` adds everything that takes runs of its own: the
+sweep-against-walk check of the edges, the K repeat steps (``repeat_*``), the per-phase step
+(``phase_ms_last_step``), the cold step, the transfer times and the CPU baselines.
 
 Workload (BASELINE.json configs[2]): 1,000,000 synthetic reads,
 1-16 fillings each (seed 11), default clustering parameters.  Inputs are resident
@@ -87,14 +94,20 @@ def parse():
     ap.add_argument('--engine', default='auto', choices=['auto', 'walk', 'sweep'],
                     help='pair engine of the timed step (fslr_hip.h FSLR_ENGINE_*); the walk engine always runs '
                          'once before timing to count the Jaccard-evaluated pairs of the input')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline does not need: the sweep-against-walk edge check, the '
+                         'repeat steps, the per-phase and cold steps, the transfer times and the CPU baselines')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last one computed (labels, forward degrees, '
+                         'edges in canonical order) as DIR/<name>.npy, float32 or float64, at most 64 MB in all')
     ap.add_argument('--sync-cap', action='store_true',
-                    help='check the edge cap with a host read in every timed step (default: on the device, '
-                         'read once after the timed steps; a step that needed the replay reruns them this way)')
+                    help='--full: check the edge cap with a host read in every repeat step (default: on the '
+                         'device, read once after those steps; a step that needed the replay reruns them this way)')
     ap.add_argument('--cpu-sample-stride', type=int, default=16,
-                    help='single-thread CPU baseline: query reads of every k-th 64-rank block (0 = skip the '
-                         'CPU baseline)')
+                    help='--full: single-thread CPU baseline: query reads of every k-th 64-rank block (0 = skip '
+                         'the CPU baseline)')
     ap.add_argument('--cpu-threads', type=int, default=0,
-                    help='threads of the all-core CPU baseline (0 = the affinity set, limited by OMP_NUM_THREADS)')
+                    help='--full: threads of the all-core CPU baseline (0 = the affinity set, limited by OMP_NUM_THREADS)')
     ap.add_argument('--verify', action='store_true',
                     help='after timing, rank 0 checks its labels against a single-context run of all reads')
     ap.add_argument('--traffic-json', default=TRAFFIC_JSON,
@@ -168,7 +181,7 @@ def main():
     a0, a1 = shard_range(csr.n_reads, rank, world)
     ctx.build_index()
     counted = ctx.run_query(qcut, ncut, pt, 10, a0, a1, engine='walk')
-    if world == 1:
+    if args.full and world == 1:
         walk_edges = sorted(zip(*[x.tolist() for x in ctx.edges(counted['n_edges'])]))
         walk_fwd = ctx.fwd_degree()
     shard = None
@@ -204,7 +217,7 @@ def main():
     torch.cuda.synchronize()
     st = ctx.stats()
     engine = st['engine']
-    if world == 1 and engine != 'walk':
+    if args.full and world == 1 and engine != 'walk':
         ctx.query(qcut, ncut, pt, 10, engine=args.engine)
         se = ctx.stats()
         same = (sorted(zip(*[x.tolist() for x in ctx.edges(se['n_edges'])])) == walk_edges and
@@ -214,9 +227,9 @@ def main():
         log(f'[rank 0] {engine} engine: edges and forward degrees identical to the walk engine')
 
     # timed regions: only the pair kernels' own events stay on the stream (profiling level 2); the
-    # per-phase events are recorded in one extra untimed step afterwards.
-    # 1. repeat steps (secondary): a query on unchanged input keeps its length-gate ranges and its entry
-    #    count on the device (no mid-step readback), the edge cap checked on the device.
+    # per-phase events are recorded in one extra untimed step afterwards (--full).
+    # 1. repeat steps (secondary, --full only): a query on unchanged input keeps its length-gate ranges and
+    #    its entry count on the device (no mid-step readback), the edge cap checked on the device.
     # 2. full-work steps (`value`): every query recomputes the gate ranges (k_len_bounds) and, on one GPU,
     #    reads its entry count back and checks the cap with a host read, as a single query on new input
     #    does; with N ranks each step still skips the host round trips (the partition's counts are checked
@@ -236,24 +249,43 @@ def main():
             dist.barrier()
         return time.perf_counter() - t0_
 
-    elapsed_rep = timed(True, True)
-    if shard is None and not args.sync_cap and ctx.edge_cap_deferred_read():
-        # a timed step's cap check fired: those steps needed the replay; time them synchronously
-        log('[rank 0] the edge cap bound in a timed step: timing synchronous steps instead')
-        args.sync_cap = True
+    elapsed_rep = None
+    if args.full:
         elapsed_rep = timed(True, True)
+        if shard is None and not args.sync_cap and ctx.edge_cap_deferred_read():
+            # a timed step's cap check fired: those steps needed the replay; time them synchronously
+            log('[rank 0] the edge cap bound in a timed step: timing synchronous steps instead')
+            args.sync_cap = True
+            elapsed_rep = timed(True, True)
     elapsed = timed(shard is not None, False)        # one GPU: full synchronous steps
     ctx.set_query_reuse(True)
+    st = ctx.stats()
+    kern = ctx.pair_kernel_times(args.steps)       # the full-work steps' main pair-kernel launches
+    kern2 = ctx.stage_kernel_times(1, args.steps) if st['engine'] == 'sweep' else np.zeros(0)   # pair stage
+    # what the last timed step left for its caller, and the transfers after the device path (not in
+    # `value`): labels / edges D2H
+    labels = d2h_labels_s = d2h_edges_s = None
+    if args.full or args.dump_outputs or args.verify:
+        t = time.perf_counter()
+        labels = shard.labels() if shard is not None else ctx.labels()
+        d2h_labels_s = time.perf_counter() - t
+    if args.full or args.dump_outputs:
+        t = time.perf_counter()
+        last_edges = ctx.edges(st['n_edges'])
+        d2h_edges_s = time.perf_counter() - t
+        if args.dump_outputs and rank == 0:
+            outputs = {'labels': labels}
+            if shard is None:                      # with N ranks a rank holds its own share of the edges only
+                outputs.update(fwd_degree=ctx.fwd_degree(), edges=canonical_edges(*last_edges))
+            dump_outputs(args.dump_outputs, outputs)
+        del last_edges
     if shard is not None:
         # the timed steps repeated the last warmup step without host syncs (SweepShard.step repeat):
         # every rank's device checks and edge counts must agree with it
         shard.verify_repeat()
-    st = ctx.stats()
-    kern = ctx.pair_kernel_times(args.steps)       # the full-work steps' main pair-kernel launches
-    kern2 = ctx.stage_kernel_times(1, args.steps) if st['engine'] == 'sweep' else np.zeros(0)   # pair stage
     lib_t = None
     cold_ms = None
-    if world == 1:
+    if args.full and world == 1:
         ctx.set_profiling(1)
         step()
         torch.cuda.synchronize()
@@ -287,7 +319,7 @@ def main():
                       'query intervals + {B_EDGE} B x edges + {B_DEFER} B x deferred entries')
     cs = counted                                      # the walk engine's counts of this rank's read range
     tot = torch.tensor([elapsed, float(cs['evaluated_pairs']), float(cs['jaccard_evals']), float(st['n_edges']),
-                        float(st['max_fwd']), elapsed_rep, float(st['matched_pairs'])], dtype=torch.float64,
+                        float(st['max_fwd']), elapsed_rep or 0.0, float(st['matched_pairs'])], dtype=torch.float64,
                        device=dev if backend == 'nccl' else 'cpu')
     capped = bool(info['capped']) if info is not None else False
     if dist:
@@ -298,6 +330,7 @@ def main():
         elapsed, max_fwd, elapsed_rep = (float(x) for x in t_max.tolist())
         max_fwd = int(max_fwd)
         pairs, jacc, n_edges, matched = (float(x) for x in sums.tolist())
+        elapsed_rep = elapsed_rep if args.full else None
     else:
         pairs, jacc, n_edges, matched = (float(x) for x in tot[[1, 2, 3, 6]].tolist())
         max_fwd = int(st['max_fwd'])
@@ -351,13 +384,7 @@ def main():
     head_roof = dict(roofs[0], phase_ms_last_step=lib_t,
                      selection='the longest kernel of the step by its HIP-event mean over the timed steps')
     # transfers around the device path (not in `value`): CSR upload before, labels / edges after
-    t = time.perf_counter()
-    labels = shard.labels() if shard is not None else ctx.labels()
-    d2h_labels_s = time.perf_counter() - t
-    t = time.perf_counter()
-    ctx.edges(st['n_edges'])
-    d2h_edges_s = time.perf_counter() - t
-    transfer = {
+    transfer = None if not args.full else {
         'upload_csr_s': upload_s, 'upload_csr_bytes': h2d_bytes,
         'd2h_labels_s': d2h_labels_s, 'd2h_edges_s': d2h_edges_s,
         'pcie_inclusive_value': jacc / (elapsed / args.steps + upload_s + d2h_labels_s + d2h_edges_s),
@@ -376,7 +403,7 @@ def main():
         log(f'[rank 0] labels identical to a single-context run: {verified}')
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_sample_stride > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample_stride > 0:
         cpu = cpu_baseline(csr, args.cpu_sample_stride, args.cpu_threads or cpu_share(), int(jacc))
 
     if rank == 0:
@@ -388,6 +415,7 @@ def main():
             'n_gpus': world,
             'steps': args.steps,
             'warmup': args.warmup,
+            'full': args.full,
             'ms_per_step': ms_per_step,
             'higher_is_better': True,
             'scaling': 'strong',
@@ -408,8 +436,8 @@ def main():
                 'kernel_evaluated_note': 'read pairs the sweep actually evaluates (>= 1 match entry: first-fit, '
                                          'U, the cut); the other Jaccard-evaluated pairs have I = 0 and are '
                                          'decided without a kernel touching them (DESIGN.md §3.6)',
-                'repeat_step_ms': 1000.0 * elapsed_rep / args.steps,
-                'repeat_value': jacc / (elapsed_rep / args.steps),
+                'repeat_step_ms': 1000.0 * elapsed_rep / args.steps if args.full else None,
+                'repeat_value': jacc / (elapsed_rep / args.steps) if args.full else None,
                 'repeat_note': 'the same step repeated on unchanged input: the length-gate ranges and the entry '
                                'count stay on the device, the edge cap is checked on the device',
                 'candidate_pairs_per_step': int(pairs),
@@ -449,6 +477,38 @@ def main():
     if dist:
         dist.destroy_process_group()
     ctx.close()
+
+
+DUMP_BUDGET = 64 * 1000 * 1000     # bytes of all dumped arrays together
+DUMP_SEED = 20240611
+
+
+def canonical_edges(a, b, inter, union):
+    """The step's edges as rows (a, b, I, U) in ascending (a, b) order: the device appends them in the
+    order its waves finish, which differs from run to run."""
+    order = np.lexsort((b, a))
+    return np.stack([np.asarray(x)[order] for x in (a, b, inter, union)], axis=1)
+
+
+def dump_outputs(dirname, arrays):
+    """Write ``arrays`` as DIR/<name>.npy: float32 where every value is an integer float32 holds exactly
+    (below 2^24), float64 otherwise.  Beyond DUMP_BUDGET bytes in all, every array keeps the same
+    fraction of its rows, chosen by a fixed seed (in ascending row order)."""
+    os.makedirs(dirname, exist_ok=True)
+    conv = {}
+    for name, x in arrays.items():
+        x = np.asarray(x)
+        small = x.size == 0 or (int(x.max()) < (1 << 24) and int(x.min()) > -(1 << 24))
+        conv[name] = x.astype(np.float32 if small else np.float64)
+    total = sum(x.nbytes for x in conv.values())
+    rng = np.random.default_rng(DUMP_SEED)
+    for name, x in conv.items():
+        if total > DUMP_BUDGET:
+            keep = int(x.shape[0] * (DUMP_BUDGET / total))
+            x = x[np.sort(rng.choice(x.shape[0], size=keep, replace=False))]
+        np.save(os.path.join(dirname, name + '.npy'), x)
+    log(f'[rank 0] outputs of the last timed step written to {dirname}: ' +
+        ', '.join(f'{n}.npy' for n in conv))
 
 
 def cpu_baseline(csr, stride, threads, gpu_jacc):

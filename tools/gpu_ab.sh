@@ -26,7 +26,7 @@ for v in "$@"; do
       -k "sweep and (synthetic or dense or locus or gate or kat or zero or capbind)" > $O/pytest_$v.log 2>&1 \
       || { echo "$v: parity failed"; tail -30 $O/pytest_$v.log; exit 1; }
   echo "$v: $(tail -1 $O/pytest_$v.log)"
-  timeout -k 10 300 python3 bench.py --steps 20 --warmup 3 --cpu-sample-stride 0 > $O/bench_$v.json 2> $O/bench_$v.log \
+  timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 3 --cpu-sample-stride 0 > $O/bench_$v.json 2> $O/bench_$v.log \
       || { tail -20 $O/bench_$v.log; exit 1; }
   python3 -c "import json; d=json.load(open('$O/bench_$v.json')); r=d['roofline']; print('$v', 'ms/step %.4f' % d['ms_per_step'], r['kernel'], 'kernel_ms %.4f' % r['kernel_ms'], r.get('phase_ms_last_step'), [(k['kernel'], round(k['kernel_ms'],4)) for k in r.get('roofline_other_kernels', [])])"
   ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $O/prof_$v -o run --output-format csv \

@@ -24,7 +24,7 @@ if has smoke; then
   tail -1 $O/smoke.log
 fi
 if has bench; then
-  timeout -k 10 400 python3 bench.py > $O/bench.json 2> $O/bench.log || { tail -20 $O/bench.log; exit 1; }
+  timeout -k 10 400 python3 bench.py --full > $O/bench.json 2> $O/bench.log || { tail -20 $O/bench.log; exit 1; }
   python3 -c "import json; d=json.load(open('$O/bench.json')); r=d['roofline']; print('value %.4e ms/step %.4f cold %s kernel %s %.4f ms frac %.3f' % (d['value'], d['ms_per_step'], d['config'].get('cold_step_ms'), r['kernel'], r['kernel_ms'], r['frac']), r.get('phase_ms_last_step'))"
 fi
 if has prof; then

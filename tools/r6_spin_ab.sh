@@ -10,7 +10,7 @@ mkdir -p $O
 cd $R
 for k in 1 2 3; do
   for v in 1 0; do
-    FSLR_SPIN_SYNC=$v timeout -k 10 300 python3 bench.py > $O/bench_spin${v}_$k.json 2> $O/bench_spin${v}_$k.log \
+    FSLR_SPIN_SYNC=$v timeout -k 10 300 python3 bench.py --full > $O/bench_spin${v}_$k.json 2> $O/bench_spin${v}_$k.log \
         || { echo "bench $v $k failed"; tail -20 $O/bench_spin${v}_$k.log; exit 1; }
     python3 -c "import json; d=json.load(open('$O/bench_spin${v}_$k.json')); print('spin$v $k', d['ms_per_step'], d['value'], d['roofline']['kernel_ms'], d['config'].get('cold_step_ms'))"
   done
