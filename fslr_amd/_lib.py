@@ -43,7 +43,8 @@ EXPORTED = ['fslr_abi_version', 'fslr_last_error', 'fslr_ctx_create', 'fslr_ctx_
             'fslr_cap_restrict', 'fslr_cap_copy_restricted', 'fslr_cap_install_restricted', 'fslr_rows_upload',
             'fslr_set_reads_rows', 'fslr_get_read_codes', 'fslr_get_csr', 'fslr_fold_thresholds',
             'fslr_position_costs', 'fslr_position_entries', 'fslr_set_position_filter', 'fslr_use_position_filter', 'fslr_long_pairs_shard',
-            'fslr_edge_cap_deferred', 'fslr_edge_cap_deferred_read', 'fslr_set_query_reuse']
+            'fslr_edge_cap_deferred', 'fslr_edge_cap_deferred_read', 'fslr_set_query_reuse',
+            'fslr_search', 'fslr_search_hits', 'fslr_search_timings']
 
 
 class HipUnavailable(RuntimeError):
@@ -204,6 +205,9 @@ def load(path: str = LIB_PATH):
         'fslr_long_pairs_shard': (ctypes.c_int, [vp, ctypes.POINTER(Params), i32, i32, ctypes.POINTER(ctypes.c_int64)]),
         'fslr_edge_cap_deferred': (ctypes.c_int, [vp, i32]),
         'fslr_edge_cap_deferred_read': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int32)]),
+        'fslr_search': (ctypes.c_int, [vp, i64, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int64)]),
+        'fslr_search_hits': (ctypes.c_int, [vp, vp, i64]),
+        'fslr_search_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -817,3 +821,35 @@ class Context:
 
     def finalize_labels(self):
         self._check(self._L.fslr_finalize_labels(self._h))
+
+    # -- batched interval search (fslr_hip.h fslr_search / fslr_search_hits) -------------------------
+    def _search(self, chrom, start, end, offsets):
+        q = [np.ascontiguousarray(x, dtype=np.int32) for x in (chrom, start, end)]
+        if not (q[0].ndim == 1 and q[0].shape == q[1].shape == q[2].shape):
+            raise ValueError('chrom, start and end must be one-dimensional and of one length')
+        total = ctypes.c_int64(0)
+        self._check(self._L.fslr_search(self._h, int(q[0].size), *(_ptr(a) for a in q),
+                                        _ptr(offsets) if offsets is not None else None, ctypes.byref(total)))
+        return int(total.value)
+
+    def search(self, chrom, start, end):
+        """The stored intervals each query (dense chromosome id, start, end; int32) hits, end-inclusive:
+        ``(offsets int64[nq + 1], hits int32[total])``, query k's hits at ``hits[offsets[k]:offsets[k + 1]]``
+        as indices into the uploaded CSR, in the search order fslr_hip.h pins (fslr_search)."""
+        offsets = np.zeros(np.asarray(chrom).size + 1, np.int64)
+        total = self._search(chrom, start, end, offsets)
+        hits = np.empty(total, np.int32)
+        self._check(self._L.fslr_search_hits(self._h, _ptr(hits), total))
+        return offsets, hits
+
+    def search_counts(self, chrom, start, end) -> np.ndarray:
+        """Hits per query, int64[nq] (fslr_search alone: no hit list is made)."""
+        offsets = np.zeros(np.asarray(chrom).size + 1, np.int64)
+        self._search(chrom, start, end, offsets)
+        return np.diff(offsets)
+
+    def search_timings(self) -> dict:
+        """HIP-event times (ms) of the last search's passes (profiling contexts)."""
+        ms = (ctypes.c_float * 4)()
+        self._check(self._L.fslr_search_timings(self._h, ms))
+        return dict(zip(('span', 'count', 'scan', 'fill'), (float(x) for x in ms)))

@@ -14,7 +14,8 @@ Function map (reference file:line → here):
   delete_false               cluster.py:80-86
   mask_sequences2            cluster.py:89-106   vectorised for IntervalData
   prepare_data               cluster.py:109-121  → IntervalData (sequence of IntervalItem)
-  build_interval_trees       cluster.py:124-130  → DeviceIntervalIndex (HBM CSR + sorted index)
+  build_interval_trees       cluster.py:124-130  → DeviceIntervalIndex (HBM CSR + sorted index);
+                             tree[chrom].search_values(start, end) (cluster.py:201) and batches of queries
   get_chromosome_lengths     cluster.py:173-175  own BGZF/BAM header reader (no pysam)
   query_interval_trees       cluster.py:187-227  device pair kernel; returns (match_df, ClusterGraph)
   get_subgraphs              cluster.py:230-234  components ordered by min read rank
@@ -37,7 +38,7 @@ from .prep import (CSR, IntervalData, IntervalItem, build_csr, data_order, first
 __all__ = ['IntervalItem', 'keep_fillings', 'rename_chromosomes', 'chrom_to_str', 'calc_coverage',
            'filter_high_coverage', 'delete_false', 'mask_sequences2', 'prepare_data', 'build_interval_trees',
            'get_chromosome_lengths', 'query_interval_trees', 'get_subgraphs', 'choose_alignment',
-           'ClusterGraph', 'DeviceIntervalIndex', 'MultiGpuIndex', 'EdgeCapWarning']
+           'ClusterGraph', 'DeviceIntervalIndex', 'ChromosomeView', 'MultiGpuIndex', 'EdgeCapWarning']
 
 
 class EdgeCapWarning(UserWarning):
@@ -200,6 +201,109 @@ class DeviceIntervalIndex:
             self.ctx.load_csr(c, thr0)
         self.ctx.build_index()
 
+    # -- search (cluster.py:201: tree[itv.chrom].search_values(itv.start, itv.end)) ----------------
+    # A query (chrom, start, end) hits the stored interval (c, s, e) iff c == chrom, s <= end and
+    # e >= start (end-inclusive, superintervals search_values).  Hits are positions in the `data` list
+    # the index was built from, in descending position of the order (start ascending, end descending,
+    # data position ascending): the search order of the superintervals stand-in
+    # (tests/golden/refharness.py), the one the edge cap is replayed in.
+    def _chrom_table(self):
+        """The caller's chromosome values -> the CSR's dense ids, made once per index: ``(keys, ids,
+        table)``, keys a sorted int64 array (or None when the values are not integers)."""
+        t = self.__dict__.get('_ctable')
+        if t is None:
+            csr = self.csr
+            dense = np.empty(csr.n_intervals, np.int64)
+            dense[np.asarray(csr.data_pos, np.int64)] = csr.iv_chrom       # per data position
+            raw = getattr(self.source, 'chrom', None)
+            raw = np.asarray([it[0] for it in self.source] if raw is None else raw)
+            keys = ids = None
+            if raw.dtype.kind in 'iu':
+                keys, first = np.unique(raw.astype(np.int64), return_index=True)
+                ids = dense[first]
+                table = dict(zip(keys.tolist(), ids.tolist()))
+            else:
+                table = {}
+                for v, d in zip(raw.tolist(), dense.tolist()):
+                    table.setdefault(v, d)
+            t = self._ctable = (keys, ids, table)
+        return t
+
+    def _dense_chroms(self, chrom) -> np.ndarray:
+        """Dense ids (int32) of the caller's chromosome values; -1 for one the index does not hold."""
+        keys, ids, table = self._chrom_table()
+        q = np.asarray(chrom)
+        if q.ndim != 1:
+            raise ValueError('chrom, start and end must be one-dimensional')
+        if keys is not None and q.dtype.kind in 'iu':
+            if not keys.size:
+                return np.full(q.shape, -1, np.int32)
+            at = np.minimum(np.searchsorted(keys, q), keys.size - 1)
+            return np.where(keys[at] == q, ids[at], -1).astype(np.int32)
+        return np.asarray([table.get(v, -1) for v in q.tolist()], np.int32)
+
+    @staticmethod
+    def _coords(x) -> np.ndarray:
+        # Stored coordinates lie in [0, 2**30): a bound below 0 selects what -1 selects and one above
+        # 2**30 what 2**30 selects, so the clip (which makes the int32 cast safe) changes no result.
+        return np.clip(np.asarray(x, dtype=np.int64), -1, 1 << 30).astype(np.int32)
+
+    def search_batch(self, chrom, start, end):
+        """The hits of a batch of query intervals: ``(offsets int64[nq + 1], data_positions int64[total])``;
+        query k's hits are ``data_positions[offsets[k]:offsets[k + 1]]`` in search order.  ``chrom`` holds
+        the caller's chromosome values (what ``data.chrom`` holds), coordinates are integers."""
+        off, hits = self.ctx.search(self._dense_chroms(chrom), self._coords(start), self._coords(end))
+        pos = np.asarray(self.csr.data_pos, np.int64)[hits]
+        if not getattr(self.csr, 'start_sorted', True) and pos.size:
+            # a list that is not start-sorted is uploaded without its data positions (the (chrom, start)
+            # sort path), so the device ranks equal (start, end) by CSR index: put those runs in data order
+            s, e = self.csr.iv_start[hits], self.csr.iv_end[hits]
+            seg = np.repeat(np.arange(off.size - 1), np.diff(off))
+            if ((seg[1:] == seg[:-1]) & (s[1:] == s[:-1]) & (e[1:] == e[:-1])).any():
+                pos = pos[np.lexsort((-pos, e, -s.astype(np.int64), seg))]
+        return off, pos
+
+    def count_batch(self, chrom, start, end) -> np.ndarray:
+        """Hits per query (int64[nq]); no hit list is made."""
+        return self.ctx.search_counts(self._dense_chroms(chrom), self._coords(start), self._coords(end))
+
+    def __getitem__(self, chrom):
+        return ChromosomeView(self, chrom)
+
+    def __contains__(self, chrom):
+        return chrom in self._chrom_table()[2]
+
+    def keys(self):
+        return self._chrom_table()[2].keys()
+
+    def items(self):
+        return [(c, ChromosomeView(self, c)) for c in self.keys()]
+
+
+class ChromosomeView:
+    """``tree[chrom]`` of a DeviceIntervalIndex: the reference's per-chromosome IntervalMap as far as
+    its pair loop uses it (cluster.py:201).  A chromosome the index does not hold gives an empty view,
+    as the reference's defaultdict gives an empty map."""
+
+    def __init__(self, index, chrom):
+        self.index, self.chrom = index, chrom
+
+    def search_idxs(self, start, end) -> np.ndarray:
+        """Data positions of the hits, in search order."""
+        if self.chrom not in self.index:
+            return np.zeros(0, np.int64)
+        return self.index.search_batch([self.chrom], [start], [end])[1]
+
+    def search_values(self, start, end) -> list:
+        """The hit intervals as items of the list the index was built from (IntervalItem)."""
+        src = self.index.source
+        return [src[p] for p in self.search_idxs(start, end).tolist()]
+
+    def count(self, start, end) -> int:
+        if self.chrom not in self.index:
+            return 0
+        return int(self.index.count_batch([self.chrom], [start], [end])[0])
+
 
 class RowsCSR:
     """The CSR fslr_set_reads_rows made on the device: the host holds what the CLI reads
@@ -256,6 +360,12 @@ class MultiGpuIndex:
         self.csr = data.csr()
         self.n_gpus = int(n_gpus)
         self.first_device = 0 if device is None else int(device)
+
+    def _no_search(self, *args, **kwargs):
+        raise NotImplementedError('a multi-GPU index lives in the rank processes and cannot be searched from here; '
+                                  'build it with n_gpus=1 to search it')
+
+    search_batch = count_batch = __getitem__ = _no_search
 
 
 def _open_context(device: int | None = None) -> Context:

@@ -177,6 +177,7 @@ void fslr_ctx_destroy(fslr_ctx* c) {
   if (c->sw_total) (void)hipHostFree(c->sw_total);
   fslr_long_free(c);
   fslr_cap_free(c);
+  fslr_search_free(c);
   if (c->ev_ok) {
     for (auto& e : c->ev) (void)hipEventDestroy(e);
     for (auto& e : c->kev) (void)hipEventDestroy(e);
@@ -905,6 +906,7 @@ int fslr_build_index(fslr_ctx* c) {
   if (c->prof_phases) HIP_TRY(c, hipEventRecord(c->ev[1], c->stream));
   c->t_index_rec = c->prof_phases;
   c->index_built = true;
+  ++c->index_gen;
   c->index_full = full;
   c->bwd_ranges = full;
   c->built_shard = c->shard;

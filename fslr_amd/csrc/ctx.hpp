@@ -175,6 +175,8 @@ struct fslr_ctx {
   bool edges_global = false;             // every E* edge is on this context (fslr_cap_install_edges)
   bool cap_gmode = false;                // gathered E* rows installed for the sharded replay (fslr_cap_install_pairs)
   struct CapWork* capw = nullptr;        // the device cap replay's buffers (cap.hip)
+  struct SearchWork* srw = nullptr;      // fslr_search's buffers and its last batch (search.hip)
+  uint64_t index_gen = 0;                // bumped by every fslr_build_index (a saved search batch belongs to one)
   // reads of more than FSLR_MAX_L intervals (long.hip): the virtual-read map and the long-pair stage
   bool lg_set = false;
   // fslr_set_reads_any: virtual interval k is real interval lg_perm[k] (thresholds arrive in the real
@@ -220,6 +222,8 @@ struct fslr_ctx {
 void fslr_long_free(fslr_ctx* c);
 // frees the cap replay's buffers (cap.hip)
 void fslr_cap_free(fslr_ctx* c);
+// frees the batched search's buffers (search.hip)
+void fslr_search_free(fslr_ctx* c);
 
 namespace fslr {
 

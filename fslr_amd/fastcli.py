@@ -314,6 +314,9 @@ class _LazyData:
     def __len__(self):
         return len(self._get())
 
+    def __getitem__(self, k):                    # the index's search_values reads items of its source
+        return self._get()[k]
+
     def __getattr__(self, name):
         if name.startswith('_'):
             raise AttributeError(name)

@@ -45,6 +45,9 @@
  *   fslr_get_long_edges   cluster.py:140-170 overall_jaccard_similarity for reads of more than
  *                         FSLR_MAX_L intervals (the reference has no limit; its l2_comparisons
  *                         scratch holds 100000 columns, :195)
+ *   fslr_search,
+ *   fslr_search_hits      cluster.py:201 tree[chrom].search_values(start, end) (superintervals
+ *                         IntervalMap), for a batch of arbitrary query intervals
  *
  * Conventions: plain C types, caller-owned host arrays, library-owned device
  * memory behind an opaque context.  Every function returns FSLR_OK (0) or an
@@ -507,6 +510,37 @@ int  fslr_get_labels(fslr_ctx *ctx, int32_t *labels);          /* [n_reads] min-
 int  fslr_get_fwd_degree(fslr_ctx *ctx, int32_t *fwd);         /* [n_reads] */
 int  fslr_get_edges(fslr_ctx *ctx, int32_t *a, int32_t *b, uint16_t *iu, int64_t capacity);
                                                                 /* iu = I | (U << 8); returns count via stats */
+
+/* Batched interval search on the built index: what the reference's pair loop asks per interval,
+ * cluster.py:201 `tree[itv.chrom].search_values(itv.start, itv.end)` (superintervals IntervalMap
+ * search_values), for n_queries arbitrary intervals at once.
+ *   Query (chrom, start, end) hits a stored interval (c, s, e) iff c == chrom, s <= end and
+ *   e >= start (end-inclusive; no order of start / end is assumed).  `chrom` is the dense id of the
+ *   uploaded CSR; an id outside [0, n_chroms) has no hits.
+ *   Order contract: a query's hits come in descending position of the order (start ascending, end
+ *   descending, data position ascending), data position = iv_data_pos[k] where the reads came with
+ *   it, else the CSR index k.  This is the search order of the superintervals stand-in
+ *   (tests/golden/refharness.py), as for fslr_apply_edge_cap; the order of the real superintervals
+ *   build may differ between its versions.  The same bytes on every run.
+ *   Reads uploaded without iv_data_pos (a list that is not start-sorted) are ranked by CSR index
+ *   where (start, end) tie, since the library never saw their data positions: a caller that wants
+ *   the list's own order there re-orders those ties itself (fslr_amd.cluster search_batch does).
+ * fslr_search counts: offsets (NULL, or [n_queries + 1]) gets the exclusive prefix of the hit counts,
+ * *n_hits (may be NULL) their total.  fslr_search_hits then writes the last fslr_search's hits, query
+ * after query: indices into the CSR the caller uploaded (fslr_set_reads / fslr_set_reads_any), or
+ * into the CSR fslr_get_csr returns (fslr_set_reads_rows).  capacity < total: FSLR_ERR_INVALID, the
+ * message carries the count, nothing is written.  n_queries == 0 is valid.  The saved batch belongs
+ * to the reads and the index build it was made on: after another fslr_set_reads* or fslr_build_index,
+ * fslr_search_hits returns FSLR_ERR_STATE until the next fslr_search.
+ * FSLR_ERR_STATE: no index built, a chromosome or position filter active, or n_shards > 1 (a partial
+ * index cannot answer).  What the search needs beyond fslr_build_index's work is built on the first
+ * search of an index; the query state (edges, labels, degrees, the cap) is left alone.  Sync. */
+int  fslr_search(fslr_ctx *ctx, int64_t n_queries, const int32_t *chrom, const int32_t *start, const int32_t *end,
+                 int64_t *offsets, int64_t *n_hits);
+int  fslr_search_hits(fslr_ctx *ctx, int32_t *hits, int64_t capacity);
+/* Profiling (fslr_set_profiling 1): HIP-event times (ms) of the last fslr_search's passes, ms[0..3] =
+ * span, count, the scans, fill (0 until fslr_search_hits ran). */
+int  fslr_search_timings(fslr_ctx *ctx, float *ms);
 
 /* Device-side views for collectives (e.g. RCCL all_gather of labels). */
 int  fslr_labels_device_ptr(fslr_ctx *ctx, void **dptr);
