@@ -44,7 +44,9 @@ EXPORTED = ['fslr_abi_version', 'fslr_last_error', 'fslr_ctx_create', 'fslr_ctx_
             'fslr_set_reads_rows', 'fslr_get_read_codes', 'fslr_get_csr', 'fslr_fold_thresholds',
             'fslr_position_costs', 'fslr_position_entries', 'fslr_set_position_filter', 'fslr_use_position_filter', 'fslr_long_pairs_shard',
             'fslr_edge_cap_deferred', 'fslr_edge_cap_deferred_read', 'fslr_set_query_reuse',
-            'fslr_search', 'fslr_search_hits', 'fslr_search_timings']
+            'fslr_search', 'fslr_search_hits', 'fslr_search_timings', 'fslr_score_pairs', 'fslr_score_timings']
+# fslr_score_pairs' flag bits (include/fslr_hip.h)
+SCORE_GATE, SCORE_EDGE, SCORE_ZD_GATE, SCORE_ZD_OVERLAP = 1, 2, 4, 8
 
 
 class HipUnavailable(RuntimeError):
@@ -208,6 +210,8 @@ def load(path: str = LIB_PATH):
         'fslr_search': (ctypes.c_int, [vp, i64, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int64)]),
         'fslr_search_hits': (ctypes.c_int, [vp, vp, i64]),
         'fslr_search_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        'fslr_score_pairs': (ctypes.c_int, [vp, ctypes.POINTER(Params), i64, vp, vp, vp, vp, vp]),
+        'fslr_score_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -853,3 +857,23 @@ class Context:
         ms = (ctypes.c_float * 4)()
         self._check(self._L.fslr_search_timings(self._h, ms))
         return dict(zip(('span', 'count', 'scan', 'fill'), (float(x) for x in ms)))
+
+    # -- pair scoring (fslr_hip.h fslr_score_pairs) --------------------------------------------------
+    def score_pairs(self, a, b, qlen_cut, nal_cut, pass_table):
+        """The pair predicates for the ordered read pairs ``(a[k], b[k])`` (ranks of the uploaded reads):
+        ``(I int32[n], U int32[n], flags uint8[n])``, flags the SCORE_* bits; the overlap thresholds are the
+        ones currently set.  ZeroDivisionError is flagged per pair, not raised."""
+        a, b = (np.ascontiguousarray(x, dtype=np.int32) for x in (a, b))
+        if not (a.ndim == 1 and a.shape == b.shape):
+            raise ValueError('a and b must be one-dimensional and of one length')
+        p = self._params(qlen_cut, nal_cut, pass_table, 0)
+        I, U, flags = np.zeros(a.size, np.int32), np.zeros(a.size, np.int32), np.zeros(a.size, np.uint8)
+        self._check(self._L.fslr_score_pairs(self._h, ctypes.byref(p), int(a.size), _ptr(a), _ptr(b), _ptr(I), _ptr(U),
+                                             _ptr(flags)))
+        return I, U, flags
+
+    def score_timings(self) -> dict:
+        """HIP-event times (ms) of the last score_pairs (profiling contexts), summed over its chunks."""
+        ms = (ctypes.c_float * 3)()
+        self._check(self._L.fslr_score_timings(self._h, ms))
+        return dict(zip(('upload', 'kernel', 'download'), (float(x) for x in ms)))

@@ -17,6 +17,10 @@ Function map (reference file:line → here):
   build_interval_trees       cluster.py:124-130  → DeviceIntervalIndex (HBM CSR + sorted index);
                              tree[chrom].search_values(start, end) (cluster.py:201) and batches of queries
   get_chromosome_lengths     cluster.py:173-175  own BGZF/BAM header reader (no pysam)
+  calculate_overlap          cluster.py:133-136  host drop-in (Python floats)
+  overall_jaccard_similarity cluster.py:140-170  host drop-in; batched on the device for arbitrary read
+                             pairs: DeviceIntervalIndex.score_pairs (fslr_score_pairs)
+  different_lengths_or_alignments cluster.py:178-183  host drop-in; the gate bit of score_pairs
   query_interval_trees       cluster.py:187-227  device pair kernel; returns (match_df, ClusterGraph)
   get_subgraphs              cluster.py:230-234  components ordered by min read rank
   choose_alignment           cluster.py:237-254  vectorised groupby/idxmax
@@ -31,14 +35,16 @@ import numpy as np
 from ._lazy import pandas as pd
 
 from . import bam_header, ingest, multi
-from ._lib import FSLR_MAX_L, FSLR_THR_ZERO_ALN, Context
+from ._lib import (FSLR_MAX_L, FSLR_THR_ZERO_ALN, SCORE_EDGE, SCORE_GATE, SCORE_ZD_GATE, SCORE_ZD_OVERLAP,
+                   Context)
 from .prep import (CSR, IntervalData, IntervalItem, build_csr, data_order, first_last_masks, fold_overlap_threshold,
                    group_span, has_long_reads, mask_keep, pass_table, umax_table)
 
 __all__ = ['IntervalItem', 'keep_fillings', 'rename_chromosomes', 'chrom_to_str', 'calc_coverage',
            'filter_high_coverage', 'delete_false', 'mask_sequences2', 'prepare_data', 'build_interval_trees',
            'get_chromosome_lengths', 'query_interval_trees', 'get_subgraphs', 'choose_alignment',
-           'ClusterGraph', 'DeviceIntervalIndex', 'ChromosomeView', 'MultiGpuIndex', 'EdgeCapWarning']
+           'ClusterGraph', 'DeviceIntervalIndex', 'ChromosomeView', 'MultiGpuIndex', 'EdgeCapWarning',
+           'calculate_overlap', 'overall_jaccard_similarity', 'different_lengths_or_alignments', 'PairScores']
 
 
 class EdgeCapWarning(UserWarning):
@@ -178,6 +184,78 @@ def get_chromosome_lengths(bam_path):
     return bam_header.get_chromosome_lengths(bam_path)
 
 
+# ------------------------------------------------------------------ pair predicates (host drop-ins)
+def calculate_overlap(interval1, interval2):
+    """cluster.py:133-136: the span the two intervals share (never below 0) as a fraction of each one's
+    aln_size; the smaller fraction.  Python floats; an aln_size of 0 raises ZeroDivisionError."""
+    shared = max(0, min(interval1.end, interval2.end) - max(interval1.start, interval2.start))
+    return min(shared / interval1.aln_size, shared / interval2.aln_size)
+
+
+def overall_jaccard_similarity(l1, l2, l2_comparisons, percentage, min_threshold):
+    """cluster.py:140-170: ``(I / U, I)`` of the first-fit matching of two interval lists.  Rows of ``l1``
+    in order; a row takes the first column of ``l2`` not yet taken that lies on its chromosome with
+    ``calculate_overlap >= percentage``; U = len(l1) + len(l2) - I.  ``l2_comparisons`` is the caller's
+    scratch: its first len(l2) entries are cleared, then set to 1 where a column was taken.  An empty
+    list gives ``(0, 0)``.  ``min_threshold`` is accepted and unused (the reference's branch on it,
+    :162-163, has no effect)."""
+    if not l1 or not l2:
+        return 0, 0
+    n_cols = len(l2)
+    l2_comparisons[:n_cols] = 0
+    n_i = 0
+    for row in l1:
+        for j in range(n_cols):
+            if l2_comparisons[j]:
+                continue
+            col = l2[j]
+            if row.chrom == col.chrom and calculate_overlap(row, col) >= percentage:
+                l2_comparisons[j] = 1
+                n_i += 1
+                break
+    union = len(l1) + n_cols - n_i
+    if union == 0:
+        return 0, 0
+    return n_i / union, n_i
+
+
+def different_lengths_or_alignments(itv1, itv2, qlen_diff, diff):
+    """cluster.py:178-183: False when the smaller qlen2 is at least ``1 - qlen_diff`` of the larger, or
+    (tested second) the smaller n_alignments at least ``1 - diff`` of the larger; True otherwise.
+    Python floats; a larger value of 0 raises ZeroDivisionError."""
+    if min(itv1.qlen2, itv2.qlen2) / max(itv1.qlen2, itv2.qlen2) >= 1 - qlen_diff:
+        return False
+    if min(itv1.n_alignments, itv2.n_alignments) / max(itv1.n_alignments, itv2.n_alignments) >= 1 - diff:
+        return False
+    return True
+
+
+class PairScores:
+    """DeviceIntervalIndex.score_pairs' result, one entry per input pair in input order: ``a``, ``b`` (read
+    ranks), ``I``, ``U`` (overall_jaccard_similarity's intersection and union), ``jaccard`` (float64 I / U,
+    0.0 where U == 0), ``gate`` (different_lengths_or_alignments is False), ``edge`` (the pair loop would
+    add the edge, cluster.py:216-221), ``zero_division`` (the reference raises for this pair: I = U = 0
+    where calculate_overlap does) and the raw ``flags`` (fslr_hip.h FSLR_SCORE_*)."""
+
+    def __init__(self, a, b, I, U, flags, qnames_by_rank):
+        self.a, self.b, self.I, self.U, self.flags = a, b, I, U, flags
+        self.qnames_by_rank = qnames_by_rank
+        self.jaccard = np.divide(I, U, out=np.zeros(I.shape, np.float64), where=U != 0)
+        self.gate = (flags & SCORE_GATE) != 0
+        self.edge = (flags & SCORE_EDGE) != 0
+        self.zero_division = (flags & (SCORE_ZD_GATE | SCORE_ZD_OVERLAP)) != 0
+
+    def __len__(self):
+        return int(self.I.shape[0])
+
+    def to_frame(self):
+        q = self.qnames_by_rank
+        n = len(self)
+        return pd.DataFrame({'query1': q[self.a] if n else np.zeros(0, object),
+                             'query2': q[self.b] if n else np.zeros(0, object),
+                             'jaccard_similarity': self.jaccard, 'n_i': self.I, 'gate': self.gate, 'edge': self.edge})
+
+
 # ------------------------------------------------------------------ device stages
 class DeviceIntervalIndex:
     """What build_interval_trees returns: the CSR in HBM plus the sorted interval index."""
@@ -266,6 +344,58 @@ class DeviceIntervalIndex:
     def count_batch(self, chrom, start, end) -> np.ndarray:
         """Hits per query (int64[nq]); no hit list is made."""
         return self.ctx.search_counts(self._dense_chroms(chrom), self._coords(start), self._coords(end))
+
+    # -- pair predicates (cluster.py:209-219) for arbitrary read pairs -----------------------------
+    def _ranks(self, query) -> np.ndarray:
+        """Read ranks (int32) of integer ranks or of qnames."""
+        q = np.asarray(query)
+        if q.ndim != 1:
+            raise ValueError('query1 and query2 must be one-dimensional')
+        if q.size == 0:
+            return np.zeros(0, np.int32)
+        if q.dtype.kind in 'iu':
+            if q.min() < 0 or q.max() >= self.csr.n_reads:
+                raise IndexError(f'read rank outside [0, {self.csr.n_reads})')
+            return q.astype(np.int32)
+        table = self.__dict__.get('_rank_of')
+        if table is None:
+            names = self.data.qnames[self.csr.read_qcode]
+            table = self._rank_of = dict(zip(names.tolist(), range(len(names))))
+        try:
+            return np.asarray([table[v] for v in q.tolist()], np.int32)
+        except KeyError as e:
+            raise KeyError(f'{e.args[0]!r} is not a read of this index') from None
+
+    def score_pairs(self, query1, query2, overlap_cutoff, jaccard_threshold, qlen_diff, diff,
+                    raise_zero_division=False) -> PairScores:
+        """What the reference's pair loop computes for the ordered read pairs ``(query1[k], query2[k])``
+        (integer read ranks, or qnames), whether or not a query would reach them: list1 = query1's
+        intervals, list2 = query2's.  One batched device call (fslr_score_pairs); the query state of the
+        index (edges, labels) is left alone.  ZeroDivisionError is flagged per pair
+        (``PairScores.zero_division``); ``raise_zero_division`` raises it for the first flagged pair."""
+        min(jaccard_threshold)                              # cluster.py:188 raises on an empty list
+        if self.long is not None:
+            raise NotImplementedError(f'score_pairs does not take an index with reads of more than {FSLR_MAX_L} '
+                                      f'intervals')
+        a, b = self._ranks(query1), self._ranks(query2)
+        if a.shape != b.shape:
+            raise ValueError('query1 and query2 must be of one length')
+        ctx = self.ctx
+        if isinstance(self, RowsIndex):
+            if self.overlap != float(overlap_cutoff):            # folded on the device at the upload
+                ctx.fold_thresholds(overlap_cutoff)
+                self.overlap = float(overlap_cutoff)
+        elif self.__dict__.get('_thr_key') != (float(overlap_cutoff), getattr(ctx, 'thr_gen', 0)):
+            ctx.set_thresholds(fold_overlap_threshold(self.csr.iv_aln, overlap_cutoff))
+            self._thr_key = (float(overlap_cutoff), ctx.thr_gen)
+        I, U, flags = ctx.score_pairs(a, b, 1 - qlen_diff, 1 - diff, pass_table(jaccard_threshold))
+        qn = self.data.qnames[self.csr.read_qcode]
+        if raise_zero_division:
+            bad = np.flatnonzero(flags & (SCORE_ZD_GATE | SCORE_ZD_OVERLAP))
+            if bad.size:
+                k = int(bad[0])
+                raise ZeroDivisionError(f'division by zero (pair {k}: {qn[a[k]]!r}, {qn[b[k]]!r})')
+        return PairScores(a, b, I, U, flags, qn)
 
     def __getitem__(self, chrom):
         return ChromosomeView(self, chrom)
@@ -366,6 +496,10 @@ class MultiGpuIndex:
                                   'build it with n_gpus=1 to search it')
 
     search_batch = count_batch = __getitem__ = _no_search
+
+    def score_pairs(self, *args, **kwargs):
+        raise NotImplementedError('a multi-GPU index lives in the rank processes and cannot score pairs from here; '
+                                  'build it with n_gpus=1 to score pairs')
 
 
 def _open_context(device: int | None = None) -> Context:

@@ -1,0 +1,292 @@
+// score.hip — the pair predicates of the reference's pair loop for a batch of arbitrary ordered read
+// pairs (cluster.py:197-224 without the search): different_lengths_or_alignments (:178-183),
+// overall_jaccard_similarity (:140-170) over calculate_overlap (:133-136) and the cutoff lookup
+// (:216-219), each pair's result written at its input position.
+//
+// Pair k = (a[k], b[k]): list1 = read a's intervals, list2 = read b's, both in CSR (data) order.  Only
+// rmeta and iv are read: no index, no query state.
+//
+// Layout: list2's columns sit on lanes; the row loop over list1 is uniform over the lane group.  Per
+// row: ballot of (column unused, same chromosome, overlap reaches both thresholds), find-first-set in
+// the group's slice of the ballot, the winner marks itself used.  No LDS, no atomics.
+// Lane-group packing: reads of the headline workload hold 1-16 intervals, so a wavefront takes four
+// consecutive pairs and gives each a 16-lane group; when one of the four has a list2 of more than 16
+// (32) intervals the wave runs its four pairs two (one) at a time on 32 (64) lanes instead.  The
+// choice is per wave and a pair never leaves its wave: outputs are not reordered.
+// List1 is loaded one record per lane of the group (chunks of the group's width) and broadcast per row.
+//
+// ZeroDivisionError is flagged, never raised: the gate's (max(qlen2) == 0, or the second ratio reached
+// with max(n_alignments) == 0) by lengths_pass; calculate_overlap's when first-fit reaches a
+// same-chromosome unused column where either interval has aln_size == 0 (thr == FSLR_THR_ZERO_ALN)
+// before the row's first match: such a column counts as a hit, and a first hit that is one ends the
+// pair with I = U = 0 (the reference stops there).
+// Algorithmic bytes per pair: 8 B of ranks + 32 B of rmeta + 16 B x (L1 + L2) in,
+// 4 B out.
+#include <algorithm>
+#include <cstdint>
+#include <cstdlib>
+#include <string>
+
+#include "ctx.hpp"
+#include "fslr_hip.h"
+#include "kernels.hpp"
+#include "wave.hpp"
+
+using namespace fslr;
+
+// the scoring scratch (grows only, bounded by the chunk) and the last call's event times
+struct ScoreWork {
+  int* ab = nullptr;                 // [2 x cap] the chunk's a, b
+  unsigned* out = nullptr;           // [cap] I | U << 8 | flags << 16
+  int64_t cap = 0;
+  unsigned char* pt = nullptr;       // [FSLR_MAX_L x kPassStride] the pass table
+  unsigned* host = nullptr;          // [host_cap] pinned: the chunk's packed results
+  int64_t host_cap = 0;
+  hipEvent_t ev[4] = {};             // upload | kernel | download boundaries of a chunk
+  bool ev_ok = false, timed = false;
+  float ms[3] = {0, 0, 0};           // summed over the last call's chunks
+};
+
+void fslr_score_free(fslr_ctx* c) {
+  ScoreWork* w = c->scw;
+  if (!w) return;
+  void* bufs[] = {w->ab, w->out, w->pt};
+  for (void* b : bufs)
+    if (b) (void)hipFree(b);
+  if (w->host) (void)hipHostFree(w->host);
+  if (w->ev_ok)
+    for (hipEvent_t e : w->ev) (void)hipEventDestroy(e);
+  delete w;
+  c->scw = nullptr;
+}
+
+namespace {
+
+constexpr int64_t kChunk = int64_t(1) << 21;   // pairs per launch: 24 MiB of scratch at most
+constexpr int kPassBytes = FSLR_MAX_L * kPassStride;
+
+struct ScoreArgs {
+  const int4* rmeta;
+  const int4* iv;
+  const unsigned char* pt;
+  const int* a;
+  const int* b;
+  unsigned* out;
+  int n_pairs, n_reads, ni;
+  double qcut, ncut;
+  int wide;                          // (timing tool) every pair on a full 64-lane group
+};
+
+struct PairMeta {
+  int offA, LA, offB, LB, gate;      // gate: FSLR_SCORE_GATE or FSLR_SCORE_ZD_GATE or 0
+};
+
+__device__ __forceinline__ PairMeta pair_meta(const ScoreArgs& s, int k, bool valid) {
+  PairMeta m{0, 0, 0, 0, 0};
+  if (valid) {
+    const int ra = s.a[k], rb = s.b[k];
+    FSLR_BOUND(ra, s.n_reads);
+    FSLR_BOUND(rb, s.n_reads);
+    const int4 ma = s.rmeta[ra], mb = s.rmeta[rb];
+    m.offA = ma.x;
+    m.LA = ma.y & 0xffff;
+    m.offB = mb.x;
+    m.LB = mb.y & 0xffff;
+    bool zd = false;
+    const bool pass = lengths_pass(ma.z, mb.z, ma.w, mb.w, s.qcut, s.ncut, &zd);
+    m.gate = zd ? FSLR_SCORE_ZD_GATE : pass ? FSLR_SCORE_GATE : 0;
+  }
+  return m;
+}
+
+// 64 / W pairs side by side, pair k on the W-lane group of this lane (valid: k is a pair)
+template <int W>
+__device__ __forceinline__ void score_groups(const ScoreArgs& s, int k, bool valid, const PairMeta& m, int lane) {
+  const int l = lane & (W - 1);
+  const int gbase = lane & ~(W - 1);
+  const bool col = valid && l < m.LB;
+  int4 bj = make_int4(-2, 0, 0, 0);
+  if (col) {
+    FSLR_BOUND(m.offB + l, s.ni);
+    bj = s.iv[m.offB + l];
+  }
+  // the row loop's bound: the longest list1 of the wave's groups (LA is uniform over a group of >= 16 lanes)
+  int max_la = valid ? m.LA : 0;
+  max_la = max(max_la, __shfl_xor(max_la, 16));
+  max_la = max(max_la, __shfl_xor(max_la, 32));
+  max_la = rdl(max_la, 0);
+  bool used = false, zd = false;
+  int I = 0;
+  for (int r0 = 0; r0 < max_la; r0 += W) {
+    int4 ai = make_int4(-1, 0, 0, 0);
+    if (valid && r0 + l < m.LA) {
+      FSLR_BOUND(m.offA + r0 + l, s.ni);
+      ai = s.iv[m.offA + r0 + l];
+    }
+    const int nr = min(W, max_la - r0);
+    for (int i = 0; i < nr; ++i) {
+      int c, si, ei, ti;
+      if constexpr (W == kWave) {
+        c = rdl(ai.x, i), si = rdl(ai.y, i), ei = rdl(ai.z, i), ti = rdl(ai.w, i);
+      } else {
+        const int src = gbase | i;
+        c = __shfl(ai.x, src), si = __shfl(ai.y, src), ei = __shfl(ai.z, src), ti = __shfl(ai.w, src);
+      }
+      const bool cand = col && !zd && r0 + i < m.LA && !used && bj.x == c;
+      // FSLR_THR_ZERO_ALN is a sentinel thr_ok would accept: tested before iv_match_general
+      const bool zero = cand && (ti == FSLR_THR_ZERO_ALN || bj.w == FSLR_THR_ZERO_ALN);
+      const bool hit = cand && (zero || iv_match_general(si, ei, ti, bj.y, bj.z, bj.w));
+      unsigned long long hm = __ballot(hit), zm = __ballot(zero);
+      if constexpr (W < kWave) {
+        hm = (hm >> gbase) & ((1ull << W) - 1);
+        zm >>= gbase;
+      }
+      if (hm) {
+        const int j = __builtin_ctzll(hm);
+        if ((zm >> j) & 1ull) {
+          zd = true;                 // the row's walk meets the aln_size == 0 column before any match
+        } else {
+          used |= l == j;
+          ++I;
+        }
+      }
+    }
+  }
+  if (valid && l == 0) {
+    int U = m.LA + m.LB - I, flags = m.gate;
+    if (zd) {
+      I = U = 0;
+      flags |= FSLR_SCORE_ZD_OVERLAP;
+    } else if ((flags & FSLR_SCORE_GATE) && I > 0) {
+      const int t = (I - 1) * kPassStride + (U - 1);
+      FSLR_BOUND(t, kPassBytes);
+      if (s.pt[t]) flags |= FSLR_SCORE_EDGE;
+    }
+    s.out[k] = static_cast<unsigned>(I) | (static_cast<unsigned>(U) << 8) | (static_cast<unsigned>(flags) << 16);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_score_pairs(ScoreArgs s) {
+  const int lane = threadIdx.x & 63;
+  const int nq = (s.n_pairs + 3) >> 2;           // a wave takes pairs [4 q, 4 q + 4)
+  const int nw = gridDim.x * (blockDim.x >> 6);
+  for (int q = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); q < nq; q += nw) {
+    const int k0 = q << 2;
+    const int k = k0 + (lane >> 4);
+    const bool valid = k < s.n_pairs;
+    const PairMeta m = pair_meta(s, k, valid);
+    const bool w64 = s.wide || __ballot(m.LB > 32) != 0;
+    const bool w32 = __ballot(m.LB > 16) != 0;
+    if (w64) {
+      for (int p = 0; p < 4 && k0 + p < s.n_pairs; ++p)
+        score_groups<64>(s, k0 + p, true, pair_meta(s, k0 + p, true), lane);
+    } else if (w32) {
+      for (int p = 0; p < 4 && k0 + p < s.n_pairs; p += 2) {
+        const int k2 = k0 + p + (lane >> 5);
+        const bool v2 = k2 < s.n_pairs;
+        score_groups<32>(s, k2, v2, pair_meta(s, k2, v2), lane);
+      }
+    } else {
+      score_groups<16>(s, k, valid, m, lane);
+    }
+  }
+}
+
+int ensure_scratch(fslr_ctx* c, ScoreWork* w, int64_t n) {
+  int rc;
+  if (!w->pt && (rc = dalloc(c, &w->pt, kPassBytes))) return rc;
+  if (n > w->cap) {
+    w->cap = 0;                                   // (a failed growth leaves no buffer behind its capacity)
+    const int64_t cap = std::min<int64_t>(kChunk, std::max<int64_t>(n + n / 4, 4096));
+    if ((rc = dalloc(c, &w->ab, 2 * cap)) || (rc = dalloc(c, &w->out, cap))) return rc;
+    w->cap = cap;
+  }
+  if (n > w->host_cap) {
+    if (w->host) (void)hipHostFree(w->host);
+    w->host = nullptr;
+    w->host_cap = 0;
+    HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&w->host), static_cast<size_t>(w->cap) * sizeof(unsigned),
+                             hipHostMallocDefault));
+    w->host_cap = w->cap;
+  }
+  return FSLR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fslr_score_pairs(fslr_ctx* c, const fslr_params* p, int64_t n_pairs, const int32_t* a, const int32_t* b,
+                     int32_t* I, int32_t* U, uint8_t* flags) {
+  if (!c) return FSLR_ERR_INVALID;
+  if (!p || !p->pass_table) return fail(c, FSLR_ERR_INVALID, "fslr_score_pairs: null params or pass_table");
+  if (n_pairs < 0) return fail(c, FSLR_ERR_INVALID, "fslr_score_pairs: negative pair count");
+  if (n_pairs && (!a || !b || !I || !U || !flags)) return fail(c, FSLR_ERR_INVALID, "fslr_score_pairs: null array");
+  if (!c->reads_set) return fail(c, FSLR_ERR_STATE, "fslr_score_pairs: fslr_set_reads first");
+  if (c->lg_set)
+    return fail(c, FSLR_ERR_INVALID, "fslr_score_pairs: the context holds reads of more than " +
+                                         std::to_string(FSLR_MAX_L) + " intervals (virtual reads), which it does not score");
+  for (int64_t k = 0; k < n_pairs; ++k) {
+    const bool bad_a = a[k] < 0 || a[k] >= c->n;
+    if (bad_a || b[k] < 0 || b[k] >= c->n)
+      return fail(c, FSLR_ERR_INVALID, std::string("fslr_score_pairs: ") + (bad_a ? "a[" : "b[") + std::to_string(k) +
+                                           "] = " + std::to_string(bad_a ? a[k] : b[k]) + " is outside [0, " +
+                                           std::to_string(c->n) + ")");
+  }
+  if (n_pairs == 0) return FSLR_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (!c->scw) c->scw = new ScoreWork();
+  ScoreWork* w = c->scw;
+  w->timed = false;
+  w->ms[0] = w->ms[1] = w->ms[2] = 0;
+  if (int rc = ensure_scratch(c, w, std::min(n_pairs, kChunk))) return rc;
+  const bool prof = c->profiling;
+  if (prof && !w->ev_ok) {
+    for (hipEvent_t& e : w->ev) HIP_TRY(c, hipEventCreate(&e));
+    w->ev_ok = true;
+  }
+  hipStream_t st = c->stream;
+  const char* wide = std::getenv("FSLR_SCORE_WIDE");       // the timing tool's comparison only
+  ScoreArgs s{c->rmeta, c->iv, w->pt, w->ab, w->ab + w->cap, w->out, 0, static_cast<int>(c->n), static_cast<int>(c->ni),
+              p->qlen_cut, p->nal_cut, wide && wide[0] == '1'};
+  for (int64_t k0 = 0; k0 < n_pairs; k0 += w->cap) {
+    const int64_t m = std::min<int64_t>(w->cap, n_pairs - k0);
+    const size_t mb = static_cast<size_t>(m) * sizeof(int);
+    if (prof) HIP_TRY(c, hipEventRecord(w->ev[0], st));
+    if (k0 == 0) HIP_TRY(c, hipMemcpyAsync(w->pt, p->pass_table, kPassBytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(w->ab, a + k0, mb, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(w->ab + w->cap, b + k0, mb, hipMemcpyHostToDevice, st));
+    if (prof) HIP_TRY(c, hipEventRecord(w->ev[1], st));
+    s.n_pairs = static_cast<int>(m);
+    k_score_pairs<<<grid_for((m + 3) / 4, 4, 256 * 32), 256, 0, st>>>(s);
+    HIP_TRY(c, hipGetLastError());
+    if (prof) HIP_TRY(c, hipEventRecord(w->ev[2], st));
+    HIP_TRY(c, hipMemcpyAsync(w->host, w->out, mb, hipMemcpyDeviceToHost, st));
+    if (prof) HIP_TRY(c, hipEventRecord(w->ev[3], st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    for (int64_t k = 0; k < m; ++k) {
+      const unsigned v = w->host[k];
+      I[k0 + k] = static_cast<int32_t>(v & 0xff);
+      U[k0 + k] = static_cast<int32_t>((v >> 8) & 0xff);
+      flags[k0 + k] = static_cast<uint8_t>(v >> 16);
+    }
+    if (prof)
+      for (int t = 0; t < 3; ++t) {
+        float ms = 0;
+        HIP_TRY(c, hipEventElapsedTime(&ms, w->ev[t], w->ev[t + 1]));
+        w->ms[t] += ms;
+      }
+  }
+  w->timed = prof;
+  return FSLR_OK;
+}
+
+int fslr_score_timings(fslr_ctx* c, float* ms) {
+  if (!c || !ms) return FSLR_ERR_INVALID;
+  ScoreWork* w = c->scw;
+  if (!w || !w->timed) return fail(c, FSLR_ERR_STATE, "fslr_score_timings: no profiled fslr_score_pairs (fslr_set_profiling 1)");
+  for (int t = 0; t < 3; ++t) ms[t] = w->ms[t];
+  return FSLR_OK;
+}
+
+}  // extern "C"

@@ -48,6 +48,10 @@
  *   fslr_search,
  *   fslr_search_hits      cluster.py:201 tree[chrom].search_values(start, end) (superintervals
  *                         IntervalMap), for a batch of arbitrary query intervals
+ *   fslr_score_pairs      cluster.py:209-219 the pair predicates of the loop for a batch of arbitrary
+ *                         ordered read pairs: different_lengths_or_alignments (:178-183),
+ *                         overall_jaccard_similarity (:140-170), calculate_overlap (:133-136) and
+ *                         the cutoff lookup (:216-219)
  *
  * Conventions: plain C types, caller-owned host arrays, library-owned device
  * memory behind an opaque context.  Every function returns FSLR_OK (0) or an
@@ -541,6 +545,39 @@ int  fslr_search_hits(fslr_ctx *ctx, int32_t *hits, int64_t capacity);
 /* Profiling (fslr_set_profiling 1): HIP-event times (ms) of the last fslr_search's passes, ms[0..3] =
  * span, count, the scans, fill (0 until fslr_search_hits ran). */
 int  fslr_search_timings(fslr_ctx *ctx, float *ms);
+
+/* The pair predicates for a batch of arbitrary ordered read pairs: what the reference's pair loop
+ * computes once its search has produced a pair (cluster.py:209-219), whether or not any query would
+ * reach that pair.  Pair k = (a[k], b[k]), ranks of the uploaded reads; list1 = read a's intervals,
+ * list2 = read b's, both in CSR (data) order; a == b is scored like any other pair.  Per pair, at its
+ * input position:
+ *   I, U     overall_jaccard_similarity's intersection and union (cluster.py:140-170): first-fit, rows
+ *            of list1 ascending, each row takes the lowest unused column of list2 on its chromosome
+ *            with calculate_overlap >= overlap; U = L1 + L2 - I.  Computed whether or not the gate
+ *            passes.
+ *   flags    FSLR_SCORE_GATE        different_lengths_or_alignments is False (cluster.py:178-183)
+ *            FSLR_SCORE_EDGE        GATE and I > 0 and pass_table[(I-1)*2*FSLR_MAX_L + (U-1)] (:216-219)
+ *            FSLR_SCORE_ZD_GATE     the gate raises ZeroDivisionError (max(qlen2) == 0, or the second
+ *                                   ratio is reached with max(n_alignments) == 0); GATE is clear
+ *            FSLR_SCORE_ZD_OVERLAP  calculate_overlap raises: first-fit reaches a same-chromosome
+ *                                   unused column where either interval has aln_size == 0 before the
+ *                                   row's first match.  The reference stops there: I = U = 0, EDGE clear.
+ * ZeroDivisionError is only flagged, never returned.  From params the call uses qlen_cut, nal_cut and
+ * pass_table (edge_threshold and flags are ignored); the overlap thresholds are the ones currently set
+ * (fslr_set_thresholds / fslr_fold_thresholds).  Host pointers; syncs.  n_pairs == 0 is valid.
+ * FSLR_ERR_STATE: no reads set.  FSLR_ERR_INVALID: a rank outside [0, n_reads) (the message names the
+ * first offending position; nothing is written), or the context holds virtual reads (fslr_set_reads_any
+ * with a read of more than FSLR_MAX_L intervals, fslr_set_long_reads): reads of more than FSLR_MAX_L
+ * intervals are out of this call's scope.  Needs only the CSR: works with or without a built index,
+ * under a chromosome or position filter and with n_shards > 1.  The query state (edges, labels, degrees,
+ * the cap, the ZeroDivisionError list, every error word) and the saved search batch are left alone.
+ * Scratch grows on demand, bounded: a large batch is processed in chunks.
+ * fslr_score_timings (fslr_set_profiling 1 or 2): HIP-event times (ms) of the last fslr_score_pairs,
+ * ms[0..2] = upload, kernel, download, summed over its chunks. */
+enum { FSLR_SCORE_GATE = 1, FSLR_SCORE_EDGE = 2, FSLR_SCORE_ZD_GATE = 4, FSLR_SCORE_ZD_OVERLAP = 8 };
+int  fslr_score_pairs(fslr_ctx *ctx, const fslr_params *params, int64_t n_pairs, const int32_t *a, const int32_t *b,
+                      int32_t *I, int32_t *U, uint8_t *flags);
+int  fslr_score_timings(fslr_ctx *ctx, float *ms);
 
 /* Device-side views for collectives (e.g. RCCL all_gather of labels). */
 int  fslr_labels_device_ptr(fslr_ctx *ctx, void **dptr);
