@@ -44,9 +44,13 @@ EXPORTED = ['fslr_abi_version', 'fslr_last_error', 'fslr_ctx_create', 'fslr_ctx_
             'fslr_set_reads_rows', 'fslr_get_read_codes', 'fslr_get_csr', 'fslr_fold_thresholds',
             'fslr_position_costs', 'fslr_position_entries', 'fslr_set_position_filter', 'fslr_use_position_filter', 'fslr_long_pairs_shard',
             'fslr_edge_cap_deferred', 'fslr_edge_cap_deferred_read', 'fslr_set_query_reuse',
-            'fslr_search', 'fslr_search_hits', 'fslr_search_timings', 'fslr_score_pairs', 'fslr_score_timings']
+            'fslr_search', 'fslr_search_hits', 'fslr_search_timings', 'fslr_score_pairs', 'fslr_score_timings',
+            'fslr_coverage_build', 'fslr_coverage_at', 'fslr_coverage_timings']
 # fslr_score_pairs' flag bits (include/fslr_hip.h)
 SCORE_GATE, SCORE_EDGE, SCORE_ZD_GATE, SCORE_ZD_OVERLAP = 1, 2, 4, 8
+# fslr_coverage_*: keys per tile of the sorted arrays, queries per chunk (include/fslr_hip.h)
+COVERAGE_TILE = 256
+COVERAGE_CHUNK = 1 << 21
 
 
 class HipUnavailable(RuntimeError):
@@ -212,6 +216,9 @@ def load(path: str = LIB_PATH):
         'fslr_search_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         'fslr_score_pairs': (ctypes.c_int, [vp, ctypes.POINTER(Params), i64, vp, vp, vp, vp, vp]),
         'fslr_score_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        'fslr_coverage_build': (ctypes.c_int, [vp, i64, i32, vp, vp, vp]),
+        'fslr_coverage_at': (ctypes.c_int, [vp, i64, vp, vp, vp]),
+        'fslr_coverage_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -877,3 +884,30 @@ class Context:
         ms = (ctypes.c_float * 3)()
         self._check(self._L.fslr_score_timings(self._h, ms))
         return dict(zip(('upload', 'kernel', 'download'), (float(x) for x in ms)))
+
+    # -- read depth at query points (fslr_hip.h fslr_coverage_build / fslr_coverage_at) --------------
+    def coverage_build(self, chrom, rstart, rend, n_chroms):
+        """Make the context's coverage set from the bed rows (dense chromosome id, rstart, rend; int32, any
+        order); it replaces the one before.  ``coverage_gen`` counts the builds that succeeded."""
+        r = [np.ascontiguousarray(x, dtype=np.int32) for x in (chrom, rstart, rend)]
+        if not (r[0].ndim == 1 and r[0].shape == r[1].shape == r[2].shape):
+            raise ValueError('chrom, rstart and rend must be one-dimensional and of one length')
+        self._check(self._L.fslr_coverage_build(self._h, int(r[0].size), int(n_chroms), *(_ptr(a) for a in r)))
+        self.coverage_gen = getattr(self, 'coverage_gen', 0) + 1
+
+    def coverage_at(self, chrom, pos) -> np.ndarray:
+        """The depth (int32) at each (dense chromosome id, position) of the batch, in input order:
+        rows with rstart <= pos less rows with rend <= pos (cluster.py:52-67)."""
+        q = [np.ascontiguousarray(x, dtype=np.int32) for x in (chrom, pos)]
+        if not (q[0].ndim == 1 and q[0].shape == q[1].shape):
+            raise ValueError('chrom and pos must be one-dimensional and of one length')
+        depth = np.zeros(q[0].size, np.int32)
+        self._check(self._L.fslr_coverage_at(self._h, int(q[0].size), _ptr(q[0]), _ptr(q[1]), _ptr(depth)))
+        return depth
+
+    def coverage_timings(self) -> dict:
+        """HIP-event times (ms) of the last coverage_build and coverage_at (profiling contexts), each summed
+        over the call's chunks."""
+        ms = (ctypes.c_float * 4)()
+        self._check(self._L.fslr_coverage_timings(self._h, ms))
+        return dict(zip(('build_upload', 'build_sort', 'query_upload_kernel', 'query_download'), (float(x) for x in ms)))

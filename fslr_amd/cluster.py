@@ -9,8 +9,11 @@ Function map (reference file:line → here):
   keep_fillings              cluster.py:14-31    vectorised first/last drop + group span
   rename_chromosomes         cluster.py:34-43    chrN by N, others after (equality-only downstream)
   chrom_to_str               cluster.py:46-49
-  calc_coverage              cluster.py:52-67
-  filter_high_coverage       cluster.py:70-77
+  calc_coverage              cluster.py:52-67    host drop-in; with device= / ctx=: DeviceCoverage, the sorted
+                             (chrom, rstart) and (chrom, rend) keys in HBM (fslr_coverage_build), depths
+                             computed for the positions asked for (device_coverage)
+  filter_high_coverage       cluster.py:70-77    host drop-in; with device= / ctx=: the depth at every
+                             (chrom, middle) in one device call (fslr_coverage_at)
   delete_false               cluster.py:80-86
   mask_sequences2            cluster.py:89-106   vectorised for IntervalData
   prepare_data               cluster.py:109-121  → IntervalData (sequence of IntervalItem)
@@ -44,7 +47,8 @@ __all__ = ['IntervalItem', 'keep_fillings', 'rename_chromosomes', 'chrom_to_str'
            'filter_high_coverage', 'delete_false', 'mask_sequences2', 'prepare_data', 'build_interval_trees',
            'get_chromosome_lengths', 'query_interval_trees', 'get_subgraphs', 'choose_alignment',
            'ClusterGraph', 'DeviceIntervalIndex', 'ChromosomeView', 'MultiGpuIndex', 'EdgeCapWarning',
-           'calculate_overlap', 'overall_jaccard_similarity', 'different_lengths_or_alignments', 'PairScores']
+           'calculate_overlap', 'overall_jaccard_similarity', 'different_lengths_or_alignments', 'PairScores',
+           'device_coverage', 'DeviceCoverage']
 
 
 class EdgeCapWarning(UserWarning):
@@ -100,8 +104,176 @@ def chrom_to_str(bed_df, chromosome_to_numeric_map):
     return bed_df
 
 
-def calc_coverage(bed_file, chromosome_lengths):
-    """cluster.py:52-67: per-chromosome +1/-1 coverage at rstart/rend, cumulative."""
+def _index_positions(pos, size, what='index'):
+    """``pos`` as numpy resolves it as an index into an axis of ``size`` (scalar or per element): values in
+    [-size, -1] wrap, anything outside [-size, size) raises IndexError at the first such element."""
+    p = np.asarray(pos)
+    if p.dtype.kind not in 'iu':
+        raise IndexError('arrays used as indices must be of integer (or boolean) type')
+    p = p.astype(np.int64)
+    size = np.broadcast_to(np.asarray(size, np.int64), p.shape)
+    bad = (p < -size) | (p >= size)
+    if bad.any():
+        k = int(np.argmax(bad))
+        raise IndexError(f'{what} {int(p.flat[k])} is out of bounds for axis 0 with size {int(size.flat[k])}')
+    return np.where(p < 0, p + size, p)
+
+
+class _ChromDepth:
+    """``cov[chrom]`` of a DeviceCoverage: reads like the reference's float64 array of ``length + 1``
+    depths, computed on the device for the positions asked for."""
+    dtype = np.dtype(np.float64)
+
+    def __init__(self, cov, dense, size):
+        self._cov, self._dense, self._size = cov, dense, size
+        self.shape = (size,)
+
+    def __len__(self):
+        return self._size
+
+    def _at(self, pos):
+        return self._cov._depth_dense(np.full(pos.shape, self._dense, np.int32), pos.astype(np.int32))
+
+    def __getitem__(self, p):
+        if isinstance(p, slice):
+            return self._at(np.arange(*p.indices(self._size), dtype=np.int64)).astype(np.float64)
+        if isinstance(p, (int, np.integer)) and not isinstance(p, (bool, np.bool_)):
+            return float(self._at(_index_positions([p], self._size))[0])
+        p = np.asarray(p)
+        if p.dtype.kind == 'b':
+            raise TypeError('DeviceCoverage takes an int, a slice or an integer array')
+        if p.size == 0:
+            return np.zeros(p.shape, np.float64)
+        return self._at(_index_positions(p.ravel(), self._size)).astype(np.float64).reshape(p.shape)
+
+
+class DeviceCoverage:
+    """What calc_coverage returns on the device path: reads like the reference's dict of per-chromosome
+    float64 arrays (cluster.py:52-67) but holds only the sorted (chrom, rstart) and (chrom, rend) keys of
+    the bed rows in HBM (fslr_coverage_build).  ``chrom in cov``, ``cov.keys()``, ``len(cov[chrom])`` and
+    ``cov[chrom][p]`` for an int, a slice or an integer array work; ``depth_at`` is the batched form."""
+
+    def __init__(self, ctx, keys, sizes, owns_ctx):
+        self.ctx, self._keys, self._sizes, self._owns_ctx = ctx, list(keys), np.asarray(sizes, np.int64), owns_ctx
+        self._ids = {k: i for i, k in enumerate(self._keys)}
+        self._gen = ctx.coverage_gen
+        self._int_keys = None
+        if self._keys and all(isinstance(k, (int, np.integer)) and not isinstance(k, bool) for k in self._keys):
+            ks = np.asarray(self._keys, np.int64)
+            order = np.argsort(ks, kind='stable')
+            self._int_keys = (ks[order], order)
+
+    def close(self):
+        """Closes the context when device_coverage made it (a caller's context stays open)."""
+        if self._owns_ctx and self.ctx is not None:
+            self.ctx.close()
+        self.ctx = None
+
+    def __contains__(self, chrom):
+        return chrom in self._ids
+
+    def __iter__(self):
+        return iter(self._keys)
+
+    def __len__(self):
+        return len(self._keys)
+
+    def keys(self):
+        return self._ids.keys()
+
+    def __getitem__(self, chrom):
+        i = self._ids[chrom]                         # KeyError as the reference's dict lookup raises it
+        return _ChromDepth(self, i, int(self._sizes[i]))
+
+    def _depth_dense(self, dense, pos):
+        if self.ctx is None:
+            raise RuntimeError('this DeviceCoverage is closed')
+        if self.ctx.coverage_gen != self._gen:
+            raise RuntimeError("the context's coverage was rebuilt since this DeviceCoverage was made")
+        return self.ctx.coverage_at(dense, pos)
+
+    def _dense_ids(self, chrom):
+        """Dense ids (int64) of chromosome labels, -1 where the coverage has none."""
+        q = np.asarray(chrom)
+        if self._int_keys is not None and q.dtype.kind in 'iu':
+            ks, order = self._int_keys
+            at = np.minimum(np.searchsorted(ks, q), ks.size - 1)
+            return np.where(ks[at] == q, order[at], -1).astype(np.int64)
+        return np.asarray([self._ids.get(v, -1) for v in q.tolist()], np.int64)
+
+    def depth_at(self, chrom, pos):
+        """``cov[chrom[k]][pos[k]]`` for every k in one device call, int32.  The errors are those of the
+        element-by-element lookups: KeyError for a chromosome without coverage, IndexError for a position
+        outside ``[-(length + 1), length]``, whichever the first offending element raises."""
+        labels = np.asarray(chrom)
+        p = np.asarray(pos)
+        if labels.ndim != 1 or labels.shape != p.shape:
+            raise ValueError('chrom and pos must be one-dimensional and of one length')
+        if p.size and p.dtype.kind not in 'iu':
+            raise IndexError('only integers, slices (`:`), ellipsis (`...`), numpy.newaxis (`None`) and integer or '
+                             'boolean arrays are valid indices')
+        p = p.astype(np.int64)
+        dense = self._dense_ids(labels) if labels.size else np.zeros(0, np.int64)
+        no_key = dense < 0
+        size = self._sizes[np.where(no_key, 0, dense)] if self._sizes.size else np.zeros(p.shape, np.int64)
+        bad = no_key | (p < -size) | (p >= size)
+        if bad.any():
+            k = int(np.argmax(bad))
+            if no_key[k]:
+                raise KeyError(labels.tolist()[k])
+            raise IndexError(f'index {int(p[k])} is out of bounds for axis 0 with size {int(size[k])}')
+        return self._depth_dense(dense.astype(np.int32), np.where(p < 0, p + size, p).astype(np.int32))
+
+
+def device_coverage(bed_file, chromosome_lengths, device=None, ctx=None) -> DeviceCoverage:
+    """calc_coverage (cluster.py:52-67) on the device.  The host does what the reference does before its
+    arithmetic: rows whose chrom is no key of ``chromosome_lengths`` (or is missing) are dropped, the
+    chromosomes that are left get dense ids in the groupby's order, and rstart / rend resolve as indices
+    into an array of ``length + 1`` (negative values wrap, anything else outside raises IndexError) before
+    anything is uploaded."""
+    codes, uniq = pd.factorize(bed_file['chrom'], sort=True)          # groupby('chrom'): sorted keys, NaN dropped
+    uniq = np.asarray(uniq, dtype=object).tolist()
+    known = np.array([u in chromosome_lengths for u in uniq], dtype=bool)
+    dense_of = np.cumsum(known) - 1
+    keys = [u for u, k in zip(uniq, known) if k]
+    sizes = np.array([int(chromosome_lengths[u]) + 1 for u in keys], np.int64)
+    if (sizes < 0).any():
+        raise ValueError('negative dimensions are not allowed')
+    if (sizes > np.iinfo(np.int32).max).any():
+        raise ValueError('the device coverage holds positions below 2**31 - 1')
+    keep = codes >= 0
+    keep[keep] = known[codes[keep]]
+    dense = dense_of[codes[keep]]
+    rs, re_ = bed_file['rstart'].to_numpy()[keep], bed_file['rend'].to_numpy()[keep]
+    if dense.size and (rs.dtype.kind not in 'iu' or re_.dtype.kind not in 'iu'):
+        raise IndexError('arrays used as indices must be of integer (or boolean) type')
+    rs, re_ = rs.astype(np.int64), re_.astype(np.int64)
+    size = sizes[dense] if dense.size else np.zeros(0, np.int64)
+    bad_s, bad_e = (rs < -size) | (rs >= size), (re_ < -size) | (re_ >= size)
+    if (bad_s | bad_e).any():
+        # np.add.at raises in the reference's order: chromosome after chromosome, rstart before rend
+        rows = np.flatnonzero(bad_s | bad_e)
+        rows = rows[dense[rows] == dense[rows].min()]
+        s_rows = rows[bad_s[rows]]
+        value = rs[s_rows[0]] if s_rows.size else re_[rows[0]]
+        raise IndexError(f'index {int(value)} is out of bounds for axis 0 with size {int(size[rows[0]])}')
+    rs, re_ = np.where(rs < 0, rs + size, rs), np.where(re_ < 0, re_ + size, re_)
+    own = ctx is None
+    ctx = ctx or Context(_default_device() if device is None else device)
+    try:
+        ctx.coverage_build(dense, rs, re_, len(keys))
+    except BaseException:
+        if own:
+            ctx.close()
+        raise
+    return DeviceCoverage(ctx, keys, sizes, own)
+
+
+def calc_coverage(bed_file, chromosome_lengths, device=None, ctx=None):
+    """cluster.py:52-67: per-chromosome +1/-1 coverage at rstart/rend, cumulative.  With ``device`` or
+    ``ctx`` given: a DeviceCoverage (nothing of the genome's length is allocated)."""
+    if device is not None or ctx is not None:
+        return device_coverage(bed_file, chromosome_lengths, device=device, ctx=ctx)
     cov = {}
     for chrom, grp in bed_file.groupby('chrom'):
         if chrom not in chromosome_lengths:
@@ -113,9 +285,21 @@ def calc_coverage(bed_file, chromosome_lengths):
     return cov
 
 
-def filter_high_coverage(data, bed_file, chromosome_lengths, threshold):
+def filter_high_coverage(data, bed_file, chromosome_lengths, threshold, device=None, ctx=None):
     """cluster.py:70-77.  (main.py:235 passes a DataFrame here, which fails in the
-    reference exactly as it fails here: iterating a DataFrame yields column names.)"""
+    reference exactly as it fails here: iterating a DataFrame yields column names.)
+    With ``device`` or ``ctx`` given the depth at every ``(chrom, middle)`` comes from one device call."""
+    if device is not None or ctx is not None:
+        cov = device_coverage(bed_file, chromosome_lengths, device=device, ctx=ctx)
+        try:
+            if isinstance(data, IntervalData):
+                return data.select(cov.depth_at(data.chrom, data.middle) <= threshold)
+            data = list(data)
+            mids = [aln.middle for aln in data]         # (a DataFrame's column names fail here, as above)
+            keep = ~(cov.depth_at(np.asarray([aln.chrom for aln in data]), np.asarray(mids)) > threshold)
+            return [aln for aln, k in zip(data, keep.tolist()) if k]
+        finally:
+            cov.close()
     cov = calc_coverage(bed_file, chromosome_lengths)
     if isinstance(data, IntervalData):
         keep = np.array([cov[c][m] <= threshold for c, m in zip(data.chrom.tolist(), data.middle.tolist())],

@@ -179,6 +179,7 @@ void fslr_ctx_destroy(fslr_ctx* c) {
   fslr_cap_free(c);
   fslr_search_free(c);
   fslr_score_free(c);
+  fslr_coverage_free(c);
   if (c->ev_ok) {
     for (auto& e : c->ev) (void)hipEventDestroy(e);
     for (auto& e : c->kev) (void)hipEventDestroy(e);

@@ -178,6 +178,7 @@ struct fslr_ctx {
   struct SearchWork* srw = nullptr;      // fslr_search's buffers and its last batch (search.hip)
   uint64_t index_gen = 0;                // bumped by every fslr_build_index (a saved search batch belongs to one)
   struct ScoreWork* scw = nullptr;       // fslr_score_pairs' scratch and its last call's times (score.hip)
+  struct CoverageWork* cvw = nullptr;    // fslr_coverage_build's resident keys, the chunk staging (coverage.hip)
   // reads of more than FSLR_MAX_L intervals (long.hip): the virtual-read map and the long-pair stage
   bool lg_set = false;
   // fslr_set_reads_any: virtual interval k is real interval lg_perm[k] (thresholds arrive in the real
@@ -227,6 +228,8 @@ void fslr_cap_free(fslr_ctx* c);
 void fslr_search_free(fslr_ctx* c);
 // frees the pair scoring's buffers (score.hip)
 void fslr_score_free(fslr_ctx* c);
+// frees the resident coverage set and its staging (coverage.hip)
+void fslr_coverage_free(fslr_ctx* c);
 
 namespace fslr {
 

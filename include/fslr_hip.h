@@ -52,6 +52,10 @@
  *                         ordered read pairs: different_lengths_or_alignments (:178-183),
  *                         overall_jaccard_similarity (:140-170), calculate_overlap (:133-136) and
  *                         the cutoff lookup (:216-219)
+ *   fslr_coverage_build,
+ *   fslr_coverage_at      cluster.py:52-77 calc_coverage / filter_high_coverage: the read depth of the
+ *                         bed rows at a batch of arbitrary (chrom, position) points, without the
+ *                         dense per-chromosome arrays
  *
  * Conventions: plain C types, caller-owned host arrays, library-owned device
  * memory behind an opaque context.  Every function returns FSLR_OK (0) or an
@@ -578,6 +582,37 @@ enum { FSLR_SCORE_GATE = 1, FSLR_SCORE_EDGE = 2, FSLR_SCORE_ZD_GATE = 4, FSLR_SC
 int  fslr_score_pairs(fslr_ctx *ctx, const fslr_params *params, int64_t n_pairs, const int32_t *a, const int32_t *b,
                       int32_t *I, int32_t *U, uint8_t *flags);
 int  fslr_score_timings(fslr_ctx *ctx, float *ms);
+
+/* Read depth at query points: the reference's calc_coverage (cluster.py:52-67) adds +1 at rstart and -1
+ * at rend of every bed row of a chromosome and takes the running sum; filter_high_coverage (:70-77)
+ * reads that sum at one position per interval.  For a chromosome c and a position p
+ *   cov[c][p] = #{rows of c with rstart <= p} - #{rows of c with rend <= p}
+ * so a row counts at its rstart and no longer at its rend, a row with rstart == rend changes nothing and
+ * a row with rstart > rend gives -1 in between.  Nothing of the genome's length is allocated.
+ * fslr_coverage_build: the n_rows bed rows as (dense chromosome id in [0, n_chroms), rstart, rend), in
+ * any order; the library keeps their sorted (chrom, rstart) and (chrom, rend) keys and every
+ * FSLR_COVERAGE_TILE-th key of each.  One resident coverage set per context: a build replaces it,
+ * fslr_ctx_destroy frees it.  n_rows == 0 is valid (depth 0 everywhere).  Host pointers; syncs.
+ * FSLR_ERR_INVALID: a chromosome id outside [0, n_chroms) or a negative position (the message names the
+ * first offending row); the resident set is unchanged, as after any other failed build.
+ * fslr_coverage_at: depth[k] = cov[chrom[k]][pos[k]] for n_queries queries in any order, each written at
+ * its input position; the same bytes on every run.  Positions beyond a chromosome's last row are valid
+ * (the library knows no lengths).  n_queries == 0 is valid.  Host pointers; syncs.  FSLR_ERR_STATE: no
+ * coverage built.  FSLR_ERR_INVALID: a chromosome id outside the build's [0, n_chroms) or a negative
+ * position (the message names the first offending query); nothing is written.  Queries go up in chunks
+ * of FSLR_COVERAGE_CHUNK: the scratch does not grow with the batch.
+ * Neither call needs fslr_set_reads or a built index, and both work under a chromosome or position
+ * filter and with n_shards > 1.  The query state (edges, labels, degrees, the cap, the ZeroDivisionError
+ * list, every error word), the saved search batch and the score scratch are left alone.
+ * fslr_coverage_timings (fslr_set_profiling 1 or 2): HIP-event times (ms) of the last calls, ms[0..3] =
+ * build upload (with the key packing), build sort (both sorts and the tile keys), query upload + kernel,
+ * query download, each summed over the call's chunks; 0 for a call that was not profiled. */
+#define FSLR_COVERAGE_TILE 256
+#define FSLR_COVERAGE_CHUNK (1 << 21)
+int  fslr_coverage_build(fslr_ctx *ctx, int64_t n_rows, int32_t n_chroms, const int32_t *chrom, const int32_t *rstart,
+                         const int32_t *rend);
+int  fslr_coverage_at(fslr_ctx *ctx, int64_t n_queries, const int32_t *chrom, const int32_t *pos, int32_t *depth);
+int  fslr_coverage_timings(fslr_ctx *ctx, float *ms);
 
 /* Device-side views for collectives (e.g. RCCL all_gather of labels). */
 int  fslr_labels_device_ptr(fslr_ctx *ctx, void **dptr);
