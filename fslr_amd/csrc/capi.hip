@@ -859,10 +859,21 @@ static int ensure_keys(fslr_ctx* c, bool keys_only) {
   return FSLR_OK;
 }
 
+// a lean index has no start column until a reader wants one: k_ranges<true> here, and after it the cap
+// replay and the batched search (both behind ensure_bwd_ranges). The walk engine and fslr_set_thresholds
+// (k_swin) come through ensure_walk_index, whose full scatter writes the column.
+static int ensure_starts(fslr_ctx* c) {
+  if (!c->index_lean || c->lean_starts) return FSLR_OK;
+  HIP_TRY(c, launch_index_starts(index_bufs(c), static_cast<int>(c->ni_idx), c->stream));
+  c->lean_starts = true;
+  return FSLR_OK;
+}
+
 int fslr::ensure_bwd_ranges(fslr_ctx* c) {
   if (!c->index_built) return fail(c, FSLR_ERR_STATE, "fslr_build_index first");
   if (c->index_full || c->bwd_ranges) return FSLR_OK;
   if (int rc = ensure_keys(c, true)) return rc;
+  if (int rc = ensure_starts(c)) return rc;
   HIP_TRY(c, launch_index_bwd_ranges(index_bufs(c), static_cast<int>(c->ni_idx), c->stream));
   c->bwd_ranges = true;
   return FSLR_OK;
@@ -904,6 +915,7 @@ int fslr_build_index(fslr_ctx* c) {
   c->idx_tt_valid = tt;
   c->index_lean = !full && index_bufs(c).dchrom && nch <= 64;
   c->lean_keys = false;
+  c->lean_starts = false;
   c->built_n_chroms = nch;
   if (c->prof_phases) HIP_TRY(c, hipEventRecord(c->ev[1], c->stream));
   c->t_index_rec = c->prof_phases;

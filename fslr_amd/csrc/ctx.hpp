@@ -25,6 +25,7 @@ struct fslr_ctx {
   bool bwd_ranges = false;                 // backward scan ranges exist (the cap replay's hits; no qpos)
   bool index_lean = false;                 // lean scatter (no data -> sorted map; `vals` holds the ends)
   bool lean_keys = false;                  // a lean index's (chrom, end) keys were made (k_endkey)
+  bool lean_starts = false;                // a lean index's start column was made (k_starts); every build clears it
   int built_n_chroms = 0;                  // chromosomes of the built index (filtered: the owned ones)
   // multi-GPU sweep: the index covers the chromosomes of a filter (fslr_set_chrom_filter)
   bool filter_active = false;
@@ -239,7 +240,9 @@ int ensure_walk_index(fslr_ctx* c);
 int peek_counts(fslr_ctx* c, long long out[4]);   // edges, err code, max_fwd, ZeroDivisionError pairs
 // the backward scan ranges of the (possibly chromosome-filtered) index, without the CSR map (capi.hip)
 int ensure_bwd_ranges(fslr_ctx* c);
-
+// the start column of a lean index (its scatter writes none) from the records, index.hip; the full
+// scatter and k_finish write it themselves
+hipError_t launch_index_starts(const IndexBufs& b, int ni, hipStream_t s);
 
 inline int fail(fslr_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg;

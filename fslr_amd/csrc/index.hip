@@ -30,6 +30,7 @@ constexpr int kRangeBlock = 256;        // threads of k_ranges
 constexpr int kRangeSpan = 1024;        // sorted positions per k_ranges block (4 per thread)
 constexpr int kTile = 256;              // pmax tiles (window edges are tile-aligned)
 constexpr int kWin = 512;
+constexpr int kLeanHalo = kWin;         // forward halo of the lean k_ranges; a window beyond it gallops
 
 __global__ void k_keys_csr(const int4* __restrict__ rmeta, const int4* __restrict__ iv, int n,
                            unsigned long long* __restrict__ keys64, int* __restrict__ vals) {
@@ -201,8 +202,9 @@ __global__ __launch_bounds__(1024) void k_chrom_scan(int* __restrict__ chist, in
 // so its cache lines fill up in one L2; with 1024-position tiles per wave the runs were ~45 long,
 // most lines were shared by waves on different XCDs and the stores cost 155 of 215 us.
 // qd[e] = q is written in data order for the CSR -> sorted position gather.
-// kFull = false (the sweep engine's lean index): the (chrom, end) key and the data -> sorted map are
-// not written (k_ranges reads each position's end from its record): 52 instead of 68 B / interval
+// kFull = false (the sweep engine's lean index): the start column, the (chrom, end) key and the
+// data -> sorted map are not written (k_ranges reads starts and ends from the records; the other
+// readers get the column from k_starts on first use): reads 28 B, writes 24 B / interval
 template <bool kFull>
 __global__ __launch_bounds__(kTileThreads) void k_chrom_scatter(const unsigned* __restrict__ dchrom,
                                                               const int4* __restrict__ drec,
@@ -264,11 +266,11 @@ __global__ __launch_bounds__(kTileThreads) void k_chrom_scatter(const unsigned* 
       const int q = runs[r & 1][c] + wp[w][c] + __popcll(mine & lt);
       idx4[q] = rec;
       idx_gate[q] = gate;
-      s_start[q] = rec.x;
       if constexpr (kFull) {
+        s_start[q] = rec.x;
         endkey[q] = (static_cast<unsigned long long>(c) << 32) | static_cast<unsigned>(rec.y);
         qd[e] = q;
-      }                                          // (lean: the end column is idx4's .y)
+      }                                          // (lean: the start and end columns are idx4's .x and .y)
     }
   }
 }
@@ -387,17 +389,37 @@ __global__ __launch_bounds__(kRangeBlock) void k_ranges(const int4* __restrict__
                                                         int2* __restrict__ rng_s, int* __restrict__ swin,
                                                         const int2* __restrict__ gate, int n_chroms = 0,
                                                         long long* __restrict__ tile_tests = nullptr) {
-  __shared__ int w_st[kRangeSpan + 2 * kWin];    // starts of [w0, w1)
+  // starts of [w0, w1); the lean flavour searches forward of q only: no backward halo
+  __shared__ int w_st[kBwd ? kRangeSpan + 2 * kWin : kRangeSpan + kLeanHalo];
   __shared__ int w_pm[kBwd ? kRangeSpan + kWin : 1];   // pmax (end part) of [w0, q0 + kRangeSpan)
   __shared__ unsigned long long t_part[kBwd ? kRangeBlock : 1];
   __shared__ int c_beg[kBwd ? 1 : 64];
   const int q0 = blockIdx.x * kRangeSpan;
   if constexpr (!kBwd)
     if (threadIdx.x < 64) c_beg[threadIdx.x] = threadIdx.x < n_chroms ? crange[threadIdx.x].x : 0x7FFFFFFF;
-  const int w0 = max(q0 - kWin, 0);              // tile-aligned
-  const int w1 = min(q0 + kRangeSpan + kWin, ni);
+  const int w0 = kBwd ? max(q0 - kWin, 0) : q0;  // tile-aligned
+  const int w1 = min(q0 + kRangeSpan + (kBwd ? kWin : kLeanHalo), ni);
   const int wp1 = min(q0 + kRangeSpan, ni);
-  for (int t = threadIdx.x; t < w1 - w0; t += kRangeBlock) w_st[t] = s_start[w0 + t];
+  // the lean build: this thread's records and gate words loaded up front (4 positions, all loads in
+  // flight together instead of one position's behind the previous one's searches); the block's own
+  // starts are the records' .x, the forward halo's come from the records of [q0 + kRangeSpan, w1)
+  // (no start column: k_chrom_scatter<false> writes none)
+  constexpr int kPerQ = kRangeSpan / kRangeBlock;
+  int4 pre4[kPerQ];
+  int2 preg[kPerQ];
+  if constexpr (kBwd) {
+    for (int t = threadIdx.x; t < w1 - w0; t += kRangeBlock) w_st[t] = s_start[w0 + t];
+  } else {
+#pragma unroll
+    for (int u = 0; u < kPerQ; ++u) {
+      const int q = q0 + threadIdx.x + u * kRangeBlock;
+      pre4[u] = q < wp1 ? idx4[q] : make_int4(0, 0, 0, 0);
+      preg[u] = q < wp1 ? gate[q] : make_int2(0, 0);
+    }
+    for (int t = kRangeSpan + threadIdx.x; t < w1 - w0; t += kRangeBlock) w_st[t] = idx4[w0 + t].x;
+#pragma unroll
+    for (int u = 0; u < kPerQ; ++u) w_st[threadIdx.x + u * kRangeBlock] = pre4[u].x;
+  }
   // pmax over [w0, wp1): prefix of the tiles before w0, then a scan of the window's keys
   if constexpr (kBwd) {
     constexpr int kPer = (kRangeSpan + kWin) / kRangeBlock;   // consecutive keys per thread
@@ -424,18 +446,7 @@ __global__ __launch_bounds__(kRangeBlock) void k_ranges(const int4* __restrict__
     }
   }
   __syncthreads();
-  // the lean build: this thread's records and gate words loaded up front (4 positions, all loads in
-  // flight together instead of one position's behind the previous one's searches)
-  constexpr int kPerQ = kRangeSpan / kRangeBlock;
-  int4 pre4[kPerQ];
-  int2 preg[kPerQ];
   if constexpr (!kBwd) {
-#pragma unroll
-    for (int u = 0; u < kPerQ; ++u) {
-      const int q = q0 + threadIdx.x + u * kRangeBlock;
-      pre4[u] = q < wp1 ? idx4[q] : make_int4(0, 0, 0, 0);
-      preg[u] = q < wp1 ? gate[q] : make_int2(0, 0);
-    }
     // The lean build writes the sweep windows only (the walk engine, the cap replay and k_swin read
     // n_fwd from k_ranges<true>'s rng_s: ensure_bwd_ranges / ensure_walk_index): one search per
     // position, for the window's bound start_p <= end_q - thr_q (cluster.py:133-136), or the whole
@@ -465,7 +476,7 @@ __global__ __launch_bounds__(kRangeBlock) void k_ranges(const int4* __restrict__
         if (lo == hi_lim && hi_lim < cr.y) {       // the window leaves the LDS span: gallop in global memory
           int step = 1;
           hi = lo;
-          while (hi < cr.y && s_start[hi] <= key) {
+          while (hi < cr.y && idx4[hi].x <= key) {
             lo = hi + 1;
             hi = lo + step;
             step <<= 1;
@@ -473,7 +484,7 @@ __global__ __launch_bounds__(kRangeBlock) void k_ranges(const int4* __restrict__
           if (hi > cr.y) hi = cr.y;
           while (lo < hi) {
             const int mid = (lo + hi) >> 1;
-            if (s_start[mid] <= key) lo = mid + 1; else hi = mid;
+            if (idx4[mid].x <= key) lo = mid + 1; else hi = mid;
           }
         }
         m = lo - q - 1;
@@ -661,11 +672,12 @@ hipError_t launch_build_index(const IndexBufs& b, int n, int ni, int n_chroms, b
     k_chrom_count<<<ntl, kTileThreads, 0, s>>>(b.dchrom, ni, ntl, rounds, b.chist);
     k_chrom_scan<<<n_chroms, 1024, 0, s>>>(b.chist, ntl, b.crange);
     if (!full) {
-      // the sweep engine's lean index: records, gate words, starts and ends, forward counts
+      // the sweep engine's lean index: records, gate words and the sweep windows (no start column:
+      // launch_index_starts makes it for the readers that want one)
       k_chrom_scatter<false><<<ntl, kTileThreads, 0, s>>>(b.dchrom, b.drec, b.dgate, b.chist, ni, ntl, rounds, b.idx4,
-                                                          b.idx_gate, b.s_start, b.endkey, b.vals);
+                                                          b.idx_gate, nullptr, b.endkey, b.vals);
       k_ranges<false><<<(ni + kRangeSpan - 1) / kRangeSpan, kRangeBlock, 0, s>>>(
-          b.idx4, b.shard, b.n_shards, b.s_start, nullptr,
+          b.idx4, b.shard, b.n_shards, nullptr, nullptr,
           TilePrefix{nullptr, nullptr}, b.crange, ni, b.rng_s, b.swin, b.idx_gate, n_chroms, b.tile_tests);
       return hipGetLastError();
     }
@@ -726,6 +738,18 @@ __global__ __launch_bounds__(256) void k_endkey(const int4* __restrict__ idx4, c
       if (c + b < 64 && c_beg[c + b] <= q) c += b;
     endkey[q] = (static_cast<unsigned long long>(c) << 32) | static_cast<unsigned>(idx4[q].y);
   }
+}
+
+// a lean index's start column from its records (k_ranges<true>, k_swin, the batched search and the cap
+// replay read one; the lean scatter writes none)
+__global__ __launch_bounds__(256) void k_starts(const int4* __restrict__ idx4, int ni, int* __restrict__ s_start) {
+  for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < ni; q += gridDim.x * blockDim.x) s_start[q] = idx4[q].x;
+}
+
+hipError_t launch_index_starts(const IndexBufs& b, int ni, hipStream_t s) {
+  if (ni <= 0) return hipSuccess;
+  k_starts<<<grid_for(ni), 256, 0, s>>>(b.idx4, ni, b.s_start);
+  return hipGetLastError();
 }
 
 hipError_t launch_index_swin(const IndexBufs& b, int ni, hipStream_t s) {
