@@ -45,7 +45,9 @@ EXPORTED = ['fslr_abi_version', 'fslr_last_error', 'fslr_ctx_create', 'fslr_ctx_
             'fslr_position_costs', 'fslr_position_entries', 'fslr_set_position_filter', 'fslr_use_position_filter', 'fslr_long_pairs_shard',
             'fslr_edge_cap_deferred', 'fslr_edge_cap_deferred_read', 'fslr_set_query_reuse',
             'fslr_search', 'fslr_search_hits', 'fslr_search_timings', 'fslr_score_pairs', 'fslr_score_timings',
-            'fslr_coverage_build', 'fslr_coverage_at', 'fslr_coverage_timings']
+            'fslr_coverage_build', 'fslr_coverage_at', 'fslr_coverage_timings',
+            'fslr_cluster_table', 'fslr_get_cluster_ids', 'fslr_get_cluster_members', 'fslr_assign_clusters',
+            'fslr_choose_representatives', 'fslr_cluster_timings']
 # fslr_score_pairs' flag bits (include/fslr_hip.h)
 SCORE_GATE, SCORE_EDGE, SCORE_ZD_GATE, SCORE_ZD_OVERLAP = 1, 2, 4, 8
 # fslr_coverage_*: keys per tile of the sorted arrays, queries per chunk (include/fslr_hip.h)
@@ -106,6 +108,13 @@ class QueryStats(ctypes.Structure):
 class CapStats(ctypes.Structure):
     _fields_ = [('applied', ctypes.c_int32), ('max_fwd', ctypes.c_int32)] + [
         (f, ctypes.c_int64) for f in ('candidates', 'capped', 'hits', 'pairs', 'dropped', 'backward')]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
+class ClusterInfo(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_int64) for f in ('n_clusters', 'n_nodes', 'max_size')]
 
     def as_dict(self):
         return {f: int(getattr(self, f)) for f, _ in self._fields_}
@@ -219,6 +228,12 @@ def load(path: str = LIB_PATH):
         'fslr_coverage_build': (ctypes.c_int, [vp, i64, i32, vp, vp, vp]),
         'fslr_coverage_at': (ctypes.c_int, [vp, i64, vp, vp, vp]),
         'fslr_coverage_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        'fslr_cluster_table': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(ClusterInfo)]),
+        'fslr_get_cluster_ids': (ctypes.c_int, [vp, vp, vp]),
+        'fslr_get_cluster_members': (ctypes.c_int, [vp, vp, vp]),
+        'fslr_assign_clusters': (ctypes.c_int, [vp, i64, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int64)]),
+        'fslr_choose_representatives': (ctypes.c_int, [vp, i64, vp, vp, vp, vp, i64, vp, vp]),
+        'fslr_cluster_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -911,3 +926,71 @@ class Context:
         ms = (ctypes.c_float * 4)()
         self._check(self._L.fslr_coverage_timings(self._h, ms))
         return dict(zip(('build_upload', 'build_sort', 'query_upload_kernel', 'query_download'), (float(x) for x in ms)))
+
+    # -- cluster table and representatives (fslr_hip.h fslr_cluster_table ...) ------------------------
+    def cluster_table(self, labels=None) -> dict:
+        """Make the context's cluster table from min-rank labels: the device labels of the last components
+        call (``labels`` None) or a host vector (int32).  Returns ``{n, n_clusters, n_nodes, max_size}``; the
+        table replaces the one before."""
+        info = ClusterInfo()
+        if labels is None:
+            self._check(self._L.fslr_cluster_table(self._h, None, 0, ctypes.byref(info)))
+            n = int(self.n_reads)
+        else:
+            lab = np.ascontiguousarray(labels, dtype=np.int32)
+            if lab.ndim != 1:
+                raise ValueError('labels must be one-dimensional')
+            n = int(lab.size)
+            # (a NULL pointer selects the device labels: an empty vector still passes an address)
+            self._check(self._L.fslr_cluster_table(self._h, _ptr(lab) if n else _ptr(np.zeros(1, np.int32)), n,
+                                                   ctypes.byref(info)))
+        self._cluster_info = dict(info.as_dict(), n=n)
+        return dict(self._cluster_info)
+
+    def cluster_ids(self):
+        """``(cid int32[n], size int32[n])`` of the table: the dense cluster id of each read rank (-1 for a
+        read alone) and the size of its component."""
+        ci = getattr(self, '_cluster_info', None) or {'n': 0}
+        cid, size = np.empty(ci['n'], np.int32), np.empty(ci['n'], np.int32)
+        self._check(self._L.fslr_get_cluster_ids(self._h, _ptr(cid), _ptr(size)))
+        return cid, size
+
+    def cluster_members(self):
+        """``(off int64[n_clusters + 1], members int32[n_nodes])``: cluster k's read ranks, ascending, are
+        ``members[off[k]:off[k + 1]]``."""
+        ci = getattr(self, '_cluster_info', None) or {'n_clusters': 0, 'n_nodes': 0}
+        off, members = np.zeros(ci['n_clusters'] + 1, np.int64), np.empty(ci['n_nodes'], np.int32)
+        self._check(self._L.fslr_get_cluster_members(self._h, _ptr(off), _ptr(members)))
+        return off, members
+
+    def assign_clusters(self, present, code_of_rank=None):
+        """main.py:334-342 over qname codes: ``(cluster int64[n_codes], n_reads int64[n_codes],
+        n_singletons)`` for ``present`` (bool per code) and the code of each read rank (None: the
+        identity)."""
+        pres = np.ascontiguousarray(present, dtype=np.uint8)
+        if pres.ndim != 1:
+            raise ValueError('present must be one-dimensional')
+        cor = None if code_of_rank is None else np.ascontiguousarray(code_of_rank, dtype=np.int64)
+        nc = int(pres.size)
+        cl, nr = np.empty(nc, np.int64), np.empty(nc, np.int64)
+        k = ctypes.c_int64(0)
+        self._check(self._L.fslr_assign_clusters(self._h, nc, _ptr(cor) if cor is not None else None, _ptr(pres),
+                                                 _ptr(cl), _ptr(nr), ctypes.byref(k)))
+        return cl, nr, int(k.value)
+
+    def choose_representatives(self, cluster, score_sum, score_cnt, first_row, n_out):
+        """cluster.py:237-254 over qname codes: ``(avg float64[n_codes], winner_code int64[n_out])``."""
+        a = [np.ascontiguousarray(x, dtype=np.int64) for x in (cluster, score_sum, score_cnt, first_row)]
+        if not (a[0].ndim == 1 and a[0].shape == a[1].shape == a[2].shape == a[3].shape):
+            raise ValueError('cluster, score_sum, score_cnt and first_row must be one-dimensional and of one length')
+        avg, win = np.empty(a[0].size, np.float64), np.empty(int(n_out), np.int64)
+        self._check(self._L.fslr_choose_representatives(self._h, int(a[0].size), *(_ptr(x) for x in a), int(n_out),
+                                                        _ptr(avg), _ptr(win)))
+        return avg, win
+
+    def cluster_timings(self) -> dict:
+        """HIP-event times (ms) of the last cluster_table, assign_clusters and choose_representatives
+        (profiling contexts)."""
+        ms = (ctypes.c_float * 3)()
+        self._check(self._L.fslr_cluster_timings(self._h, ms))
+        return dict(zip(('table', 'assign', 'choose'), (float(x) for x in ms)))

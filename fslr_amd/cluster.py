@@ -25,8 +25,10 @@ Function map (reference file:line → here):
                              pairs: DeviceIntervalIndex.score_pairs (fslr_score_pairs)
   different_lengths_or_alignments cluster.py:178-183  host drop-in; the gate bit of score_pairs
   query_interval_trees       cluster.py:187-227  device pair kernel; returns (match_df, ClusterGraph)
-  get_subgraphs              cluster.py:230-234  components ordered by min read rank
-  choose_alignment           cluster.py:237-254  vectorised groupby/idxmax
+  get_subgraphs              cluster.py:230-234  components ordered by min read rank; with ctx=: the sets from
+                             the device member CSR (fslr_cluster_table); cluster_table gives the table itself
+  choose_alignment           cluster.py:237-254  vectorised groupby/idxmax; with ctx=: the per-cluster argmax on
+                             the device (fslr_choose_representatives)
 """
 from __future__ import annotations
 
@@ -48,7 +50,7 @@ __all__ = ['IntervalItem', 'keep_fillings', 'rename_chromosomes', 'chrom_to_str'
            'get_chromosome_lengths', 'query_interval_trees', 'get_subgraphs', 'choose_alignment',
            'ClusterGraph', 'DeviceIntervalIndex', 'ChromosomeView', 'MultiGpuIndex', 'EdgeCapWarning',
            'calculate_overlap', 'overall_jaccard_similarity', 'different_lengths_or_alignments', 'PairScores',
-           'device_coverage', 'DeviceCoverage']
+           'device_coverage', 'DeviceCoverage', 'ClusterTable', 'cluster_table']
 
 
 class EdgeCapWarning(UserWarning):
@@ -955,17 +957,59 @@ def _query_multi_gpu(mg, thr, jaccard_threshold, edge_threshold, qlen_diff, diff
     return RawGraph(data, csr, np.asarray(r['labels']), a, b, I, U, r['fwd'], st)
 
 
-def get_subgraphs(G):
-    """cluster.py:230-234: connected components, in the reference's order (by min read rank)."""
+class ClusterTable:
+    """The cluster table of a label vector (fslr_cluster_table), on the host: ``cid[r]`` the dense id of
+    read rank r's component among the components of two or more reads in networkx order (ascending smallest
+    rank), -1 for a read alone; ``size[r]`` its component's size; ``roots[k]`` cluster k's smallest rank;
+    cluster k's ranks, ascending, are ``members[off[k]:off[k + 1]]``."""
+
+    def __init__(self, cid, size, off, members, info):
+        self.cid, self.size, self.off, self.members = cid, size, off, members
+        self.n_clusters, self.n_nodes, self.max_size = info['n_clusters'], info['n_nodes'], info['max_size']
+        self.roots = members[off[:-1]]
+
+    def __len__(self):
+        return int(self.n_clusters)
+
+
+def _labels_of(G_or_labels):
+    return np.asarray(getattr(G_or_labels, 'labels', G_or_labels))
+
+
+def cluster_table(G_or_labels, ctx=None, device=None) -> ClusterTable:
+    """The ClusterTable of a ClusterGraph, a RawGraph or a vector of min-rank labels, made on the device.
+    The table stays resident in ``ctx`` (Context.assign_clusters reads it); without ``ctx`` a context on
+    ``device`` is opened for the call."""
+    labels = _labels_of(G_or_labels)
+    own = ctx is None
+    ctx = ctx or Context(_default_device() if device is None else device)
+    try:
+        info = ctx.cluster_table(labels)
+        cid, size = ctx.cluster_ids()
+        off, members = ctx.cluster_members()
+    finally:
+        if own:
+            ctx.close()
+    return ClusterTable(cid, size, off, members, info)
+
+
+def get_subgraphs(G, ctx=None):
+    """cluster.py:230-234: connected components, in the reference's order (by min read rank).  With ``ctx``
+    the sets come from the device member CSR (fslr_cluster_table)."""
     if isinstance(G, ClusterGraph):
+        if ctx is not None:
+            t = cluster_table(G, ctx=ctx)
+            names, off = G.qnames_by_rank[t.members].tolist() if t.n_nodes else [], t.off.tolist()
+            return [set(names[off[k]:off[k + 1]]) for k in range(t.n_clusters)]
         return G.components()
     import networkx as nx
     return list(nx.connected_components(G))
 
 
-def choose_alignment(bed_file):
-    """cluster.py:237-254: per cluster the read with the highest mean alignment_score (first on ties)."""
-    fast = _choose_alignment_codes(bed_file)
+def choose_alignment(bed_file, ctx=None):
+    """cluster.py:237-254: per cluster the read with the highest mean alignment_score (first on ties).
+    With ``ctx`` (and a frame _choose_alignment_codes takes) the per-cluster argmax runs on the device."""
+    fast = _choose_alignment_codes(bed_file, ctx)
     if fast is not None:
         return fast
     avg = bed_file.groupby('qname')['alignment_score'].mean()
@@ -975,7 +1019,7 @@ def choose_alignment(bed_file):
     return bed_file[bed_file['qname'].isin(chosen)]
 
 
-def _choose_alignment_codes(bed_file):
+def _choose_alignment_codes(bed_file, ctx=None):
     """choose_alignment from the reader's qname codes (ingest.QnameCodes), for an int64
     alignment_score and numeric cluster ids, or None.
 
@@ -983,7 +1027,8 @@ def _choose_alignment_codes(bed_file):
     order (pandas' compensated sum included), divided by the count, so bincount gives the same
     doubles.  groupby('cluster').idxmax() = the first row (in frame order) holding its cluster's
     maximum; scores and clusters are constant per qname, so it is the earliest first row among
-    the cluster's qnames with the maximal mean."""
+    the cluster's qnames with the maximal mean.  With ``ctx`` the means and that argmax come from
+    fslr_choose_representatives (the same doubles: one IEEE division per qname)."""
     if not isinstance(bed_file.attrs.get(ingest.ATTR), ingest.QnameCodes) or 'cluster' not in bed_file:
         return None
     score = bed_file['alignment_score'].to_numpy()
@@ -997,9 +1042,6 @@ def _choose_alignment_codes(bed_file):
     sums = np.bincount(codes, weights=score.astype(np.float64), minlength=nq)
     cnt = np.bincount(codes, minlength=nq)
     avg_q = sums / cnt
-    with warnings.catch_warnings():
-        warnings.simplefilter('ignore')
-        bed_file['avg_alignment_score'] = avg_q[codes]
     first_row = np.full(nq, -1, dtype=np.int64)
     first_row[codes[::-1]] = np.arange(len(codes) - 1, -1, -1)
     cl_q = cl[first_row]
@@ -1010,6 +1052,15 @@ def _choose_alignment_codes(bed_file):
         return None
     cid = cl_q.astype(np.int64)
     k = int(cid.max()) + 1
+    if ctx is not None:
+        avg_q, win = ctx.choose_representatives(cid, sums.astype(np.int64), cnt, first_row, k)
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        bed_file['avg_alignment_score'] = avg_q[codes]
+    if ctx is not None:
+        chosen = np.zeros(nq, dtype=bool)
+        chosen[win[win >= 0]] = True
+        return bed_file[chosen[codes]]
     best = np.full(k, -np.inf)
     np.maximum.at(best, cid, avg_q)
     cand = np.flatnonzero(avg_q == best[cid])

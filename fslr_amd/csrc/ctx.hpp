@@ -180,6 +180,7 @@ struct fslr_ctx {
   uint64_t index_gen = 0;                // bumped by every fslr_build_index (a saved search batch belongs to one)
   struct ScoreWork* scw = nullptr;       // fslr_score_pairs' scratch and its last call's times (score.hip)
   struct CoverageWork* cvw = nullptr;    // fslr_coverage_build's resident keys, the chunk staging (coverage.hip)
+  struct ClusterWork* clw = nullptr;     // fslr_cluster_table's resident table, the assign / representatives scratch (clusters.hip)
   // reads of more than FSLR_MAX_L intervals (long.hip): the virtual-read map and the long-pair stage
   bool lg_set = false;
   // fslr_set_reads_any: virtual interval k is real interval lg_perm[k] (thresholds arrive in the real
@@ -231,6 +232,8 @@ void fslr_search_free(fslr_ctx* c);
 void fslr_score_free(fslr_ctx* c);
 // frees the resident coverage set and its staging (coverage.hip)
 void fslr_coverage_free(fslr_ctx* c);
+// frees the resident cluster table and its scratch (clusters.hip)
+void fslr_cluster_free(fslr_ctx* c);
 
 namespace fslr {
 

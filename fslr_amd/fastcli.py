@@ -193,25 +193,21 @@ def _run(args, basename, tsv, ints, strs, t, pool, ctx_f, state):
         return False
 
     t3 = time.perf_counter()
-    # main.py:251-342 assign_clusters: components by min rank (networkx order), then the qnames
-    # without an edge in first-appearance order, n_reads 1; float columns when any such qname
-    lab = g.labels
-    nr = lab.shape[0]
-    sizes = np.bincount(lab, minlength=nr)
-    roots = np.flatnonzero(sizes >= 2)
-    rid = np.full(nr, -1, np.int64)
-    rid[roots] = np.arange(roots.size)
-    node = sizes[lab] >= 2
-    q_cid = np.full(n_q, -1, np.int64)
-    q_size = np.zeros(n_q, np.int64)
-    rq = csr.read_qcode[node]
-    q_cid[rq] = rid[lab[node]]
-    q_size[rq] = sizes[lab[node]]
-    present, keys, key_of_code, avg, first_row = w
-    single = present & (q_cid < 0)
-    k = int(single.sum())
-    q_cid[single] = roots.size + np.arange(k)
-    q_size[single] = 1
+    present, keys, key_of_code, avg, first_row, sums, cnt = w
+    # main.py:251-342 assign_clusters.  A query that ran on one live single-GPU context without virtual
+    # reads left its labels on the device: the table, the numbering and the representatives are made there
+    # (fslr_cluster_table, fslr_assign_clusters, fslr_choose_representatives).  The multi-GPU index, long
+    # reads and any FslrError of those calls take the host block.
+    dctx = _table_context(trees, g)
+    q_cid = None
+    if dctx is not None:
+        try:
+            n_cl = dctx.cluster_table()['n_clusters']
+            q_cid, q_size, k = dctx.assign_clusters(present, csr.read_qcode)
+        except FslrError:
+            dctx = q_cid = None
+    if q_cid is None:
+        q_cid, q_size, k, n_cl = _assign_host(g.labels, csr.read_qcode, present, n_q)
     cl_k, nr_k = q_cid[keys], q_size[keys]
     if k:
         cl_k, nr_k = cl_k.astype(np.float64), nr_k.astype(np.float64)
@@ -224,14 +220,17 @@ def _run(args, basename, tsv, ints, strs, t, pool, ctx_f, state):
                              ['cluster', 'n_reads'], [cl_k, nr_k])
         # cluster.py:237-254 choose_alignment: per cluster the qname with the highest mean score, the
         # first in file order on ties; its rows
-        cid_k = q_cid[keys]
-        best = np.full(int(cid_k.max()) + 1, -np.inf)
-        np.maximum.at(best, cid_k, avg[keys])
-        cand = keys[avg[keys] == best[cid_k]]
-        win = np.full(best.size, rows.size, np.int64)
-        np.minimum.at(win, q_cid[cand], first_row[cand])
-        chosen = np.zeros(n_q, bool)
-        chosen[qc[win[win < rows.size]]] = True
+        chosen = None
+        if dctx is not None:
+            try:
+                avg_d, win_code = dctx.choose_representatives(np.where(present, q_cid, -1), sums.astype(np.int64), cnt,
+                                                              first_row, n_cl + k)
+                chosen = np.zeros(n_q, bool)
+                chosen[win_code[win_code >= 0]] = True
+            except FslrError:
+                chosen = None
+        if chosen is None:
+            chosen = _choose_host(q_cid, keys, avg, first_row, qc, rows.size, n_q)
         rsel = chosen[qc]
         t['write.choose'] = time.perf_counter() - t3 - t['write.assign']
         fut_r = wpool.submit(_write, tsv, f'{basename}.mappings.representative.bed', rows[rsel], key_of_code[qc[rsel]],
@@ -257,11 +256,56 @@ def _run(args, basename, tsv, ints, strs, t, pool, ctx_f, state):
     return True
 
 
+def _table_context(trees, g):
+    """The context whose device labels are the graph's: a single-GPU index without virtual reads, still open."""
+    ctx = getattr(trees, 'ctx', None)
+    if not isinstance(trees, cluster.DeviceIntervalIndex) or trees.long is not None or ctx is None:
+        return None
+    if not getattr(ctx, '_h', None) or g.labels.shape[0] != ctx.n_reads:
+        return None
+    return ctx
+
+
+def _assign_host(lab, read_qcode, present, n_q):
+    """main.py:251-342 assign_clusters on the host: components by min rank (networkx order), then the
+    qnames without an edge in first-appearance order, n_reads 1.  Returns (q_cid, q_size, k, n_clusters)."""
+    nr = lab.shape[0]
+    sizes = np.bincount(lab, minlength=nr)
+    roots = np.flatnonzero(sizes >= 2)
+    rid = np.full(nr, -1, np.int64)
+    rid[roots] = np.arange(roots.size)
+    node = sizes[lab] >= 2
+    q_cid = np.full(n_q, -1, np.int64)
+    q_size = np.zeros(n_q, np.int64)
+    rq = read_qcode[node]
+    q_cid[rq] = rid[lab[node]]
+    q_size[rq] = sizes[lab[node]]
+    single = present & (q_cid < 0)
+    k = int(single.sum())
+    q_cid[single] = roots.size + np.arange(k)
+    q_size[single] = 1
+    return q_cid, q_size, k, int(roots.size)
+
+
+def _choose_host(q_cid, keys, avg, first_row, qc, n_rows, n_q):
+    """cluster.py:237-254 choose_alignment on the host: per cluster the qname with the highest mean score,
+    the first in file order on ties."""
+    cid_k = q_cid[keys]
+    best = np.full(int(cid_k.max()) + 1, -np.inf)
+    np.maximum.at(best, cid_k, avg[keys])
+    cand = keys[avg[keys] == best[cid_k]]
+    win = np.full(best.size, n_rows, np.int64)
+    np.minimum.at(win, q_cid[cand], first_row[cand])
+    chosen = np.zeros(n_q, bool)
+    chosen[qc[win[win < n_rows]]] = True
+    return chosen
+
+
 def _writer_prep(qc, n_q, score):
     """What the writers need that does not depend on the graph: the qnames present (ascending code =
     first-appearance order) and their key numbers, each qname's mean alignment_score
     (choose_alignment's groupby mean: a float64 sum of int64 values below 2**53 is exact in any
-    order) and its first row."""
+    order), its first row, and the sums and counts behind the means."""
     present = np.zeros(n_q, bool)
     present[qc] = True
     keys = np.flatnonzero(present)
@@ -277,7 +321,7 @@ def _writer_prep(qc, n_q, score):
         first_row[qc[st]] = st
     else:
         np.minimum.at(first_row, qc, np.arange(qc.size))
-    return present, keys, key_of_code, avg, first_row
+    return present, keys, key_of_code, avg, first_row, sums, cnt
 
 
 def _run_starts(codes):

@@ -32,7 +32,7 @@ PRIMER_SEQS = {'21q1': 'CTACCTCTCTCGACACCAAG', '17p6': 'GGCTGAACTATAGCCTCTGC', '
                '16p1': 'CTGCCCTAGAAGTGAGAAGTCCA', 'M613': 'GGAGGAAAGCATGTTTCTGAG', 'M615': 'TAGTGGACAAACACGAGAGGC'}
 
 
-def assign_clusters(bed_file: pd.DataFrame, G: cluster.ClusterGraph):
+def assign_clusters(bed_file: pd.DataFrame, G: cluster.ClusterGraph, ctx=None):
     """main.py:251-342: add ``cluster`` / ``n_reads`` columns to ``bed_file`` (in place).
 
     Clustered reads get their component index (components ordered by min read
@@ -40,8 +40,25 @@ def assign_clusters(bed_file: pd.DataFrame, G: cluster.ClusterGraph):
     other qname of ``bed_file`` gets the next ids in first-appearance order with
     n_reads 1.  Both columns are float when any such singleton exists (the
     reference's left merge introduces NaN before fillna), int otherwise.
+    With ``ctx`` (a fslr_amd._lib.Context) the table and the numbering are made on the device
+    (fslr_cluster_table, fslr_assign_clusters).
     """
     codes, uniq = ingest.factorize_qname(bed_file)
+    if ctx is not None:
+        if codes.size and (codes < 0).any():
+            raise ValueError('missing qname values are not supported')
+        nu = len(uniq)
+        code_of_rank = pd.Index(uniq, dtype=object).get_indexer(pd.Index(G.qnames_by_rank, dtype=object)).astype(np.int64)
+        away = code_of_rank < 0                       # a read of the graph without rows here: a code of its own
+        code_of_rank[away] = nu + np.arange(int(away.sum()))
+        present = np.zeros(nu + int(away.sum()), np.uint8)
+        present[:nu] = 1
+        ctx.cluster_table(G.labels)
+        cl, nr, k = ctx.assign_clusters(present, code_of_rank)
+        dtype = np.float64 if k else np.int64
+        bed_file['cluster'] = cl[codes].astype(dtype)
+        bed_file['n_reads'] = nr[codes].astype(dtype)
+        return bed_file
     rank_names = G.qnames_by_rank
     node = G.node_mask
     cid_by_name = pd.Series(G.component_id[node], index=pd.Index(rank_names[node], dtype=object))

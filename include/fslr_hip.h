@@ -56,6 +56,15 @@
  *   fslr_coverage_at      cluster.py:52-77 calc_coverage / filter_high_coverage: the read depth of the
  *                         bed rows at a batch of arbitrary (chrom, position) points, without the
  *                         dense per-chromosome arrays
+ *   fslr_cluster_table,
+ *   fslr_get_cluster_ids,
+ *   fslr_get_cluster_members  cluster.py:230-234 get_subgraphs as a table over read ranks: the components of
+ *                         >= 2 reads numbered in networkx order (ascending smallest rank), every read's
+ *                         component id and size, and each component's reads
+ *   fslr_assign_clusters  main.py:251-342 assign_clusters (the numbering of main.py:334-342) over qname codes
+ *   fslr_choose_representatives
+ *                         cluster.py:237-254 choose_alignment: per cluster the qname with the highest mean
+ *                         alignment_score, the first in frame order on ties (idxmax)
  *
  * Conventions: plain C types, caller-owned host arrays, library-owned device
  * memory behind an opaque context.  Every function returns FSLR_OK (0) or an
@@ -613,6 +622,59 @@ int  fslr_coverage_build(fslr_ctx *ctx, int64_t n_rows, int32_t n_chroms, const 
                          const int32_t *rend);
 int  fslr_coverage_at(fslr_ctx *ctx, int64_t n_queries, const int32_t *chrom, const int32_t *pos, int32_t *depth);
 int  fslr_coverage_timings(fslr_ctx *ctx, float *ms);
+
+/* The cluster table: what the reference rebuilds on the host from the connected components
+ * (get_subgraphs, cluster.py:230-234; assign_clusters, main.py:251-342; choose_alignment,
+ * cluster.py:237-254), from min-rank labels on the device.
+ * fslr_cluster_table: labels == NULL takes the context's device labels (the parents after fslr_components,
+ *   fslr_components_from_pairs, fslr_local_forest or fslr_finalize_labels; n is ignored): FSLR_ERR_STATE
+ *   without reads, after an overflowed query (as fslr_get_labels) or when the labels are not final;
+ *   FSLR_ERR_INVALID when the context holds virtual reads (as fslr_score_pairs; pass their labels from the
+ *   host).  labels != NULL takes a host vector of n <= 2^30 min-rank labels (the multi-GPU and long-read
+ *   paths hold theirs on the host); it needs no reads and no index.  The labels are checked on the device:
+ *   labels[r] must lie in [0, r] and labels[labels[r]] == labels[r]; FSLR_ERR_INVALID names the first
+ *   offending r and the resident table is unchanged.
+ *   The table: size[r] = reads of r's component; cid[r] = the position of its root among the roots with
+ *   size >= 2 in ascending root order (networkx's component order), -1 where size == 1; the member CSR
+ *   lists each cluster's ranks ascending (its first member is its root).  One resident table per context:
+ *   a call replaces it, fslr_ctx_destroy frees it.  n == 0 is valid.  The same bytes on every run.  Syncs;
+ *   info may be NULL.  The query state, the saved search batch, the score scratch and the coverage set are
+ *   left alone.
+ * fslr_get_cluster_ids / fslr_get_cluster_members: D2H of the table (NULL outputs are skipped);
+ *   FSLR_ERR_STATE without a table.
+ * fslr_assign_clusters (main.py:334-342 in qname-code space): code_of_rank[n] = the qname code of each read
+ *   rank (NULL: the identity, n_codes == n), present[n_codes] marks the codes that have rows in the bed
+ *   file.  A present code whose rank has cid >= 0 gets that cid and size; every other present code gets
+ *   n_clusters + k, k = its index among such codes in ascending code order (first-appearance order), and
+ *   size 1; absent codes get -1 / 0.  *n_singletons (may be NULL) = the count of those other codes; the
+ *   caller applies the reference's dtype rule (float columns when it is not 0).  FSLR_ERR_STATE without a
+ *   table.  FSLR_ERR_INVALID for a code outside [0, n_codes) or a code a lower rank names too: the
+ *   message names the first offending rank and nothing is written.  Host pointers; syncs.
+ * fslr_choose_representatives (cluster.py:237-254 in code space; independent of the resident table):
+ *   codes with cluster < 0 or score_cnt == 0 are skipped, their avg is NaN; for the others avg[c] =
+ *   (double)score_sum[c] / (double)score_cnt[c] in IEEE double on the device.  winner_code[k], k < n_out,
+ *   = the code with the largest avg in cluster k, ties to the smallest first_row (idxmax: the first row
+ *   in frame order), -1 for a cluster without a code.  FSLR_ERR_INVALID for |score_sum| >= 2^53 (the
+ *   float64 sum of such scores would not be exact), cluster >= n_out or score_cnt < 0, of any code: the
+ *   message names the first offender and nothing is written.  Host pointers; syncs; every array goes up
+ *   and down through a bounded pinned chunk.
+ * fslr_cluster_timings (fslr_set_profiling 1 or 2): HIP-event times (ms), first to last operation on the
+ *   stream, of the last fslr_cluster_table, fslr_assign_clusters and fslr_choose_representatives (ms[0..2];
+ *   0 for a call that was not profiled). */
+typedef struct {
+    int64_t n_clusters;            /* components of >= 2 reads */
+    int64_t n_nodes;               /* reads in them (G.number_of_nodes()) */
+    int64_t max_size;              /* largest component, 0 if none */
+} fslr_cluster_info;
+int  fslr_cluster_table(fslr_ctx *ctx, const int32_t *labels, int64_t n, fslr_cluster_info *info);
+int  fslr_get_cluster_ids(fslr_ctx *ctx, int32_t *cid, int32_t *size);                  /* [n] each */
+int  fslr_get_cluster_members(fslr_ctx *ctx, int64_t *off, int32_t *members);           /* [n_clusters + 1], [n_nodes] */
+int  fslr_assign_clusters(fslr_ctx *ctx, int64_t n_codes, const int64_t *code_of_rank, const uint8_t *present,
+                          int64_t *cluster, int64_t *n_reads, int64_t *n_singletons);
+int  fslr_choose_representatives(fslr_ctx *ctx, int64_t n_codes, const int64_t *cluster, const int64_t *score_sum,
+                                 const int64_t *score_cnt, const int64_t *first_row, int64_t n_out, double *avg,
+                                 int64_t *winner_code);
+int  fslr_cluster_timings(fslr_ctx *ctx, float *ms);
 
 /* Device-side views for collectives (e.g. RCCL all_gather of labels). */
 int  fslr_labels_device_ptr(fslr_ctx *ctx, void **dptr);
