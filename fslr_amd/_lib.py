@@ -47,12 +47,15 @@ EXPORTED = ['fslr_abi_version', 'fslr_last_error', 'fslr_ctx_create', 'fslr_ctx_
             'fslr_search', 'fslr_search_hits', 'fslr_search_timings', 'fslr_score_pairs', 'fslr_score_timings',
             'fslr_coverage_build', 'fslr_coverage_at', 'fslr_coverage_timings',
             'fslr_cluster_table', 'fslr_get_cluster_ids', 'fslr_get_cluster_members', 'fslr_assign_clusters',
-            'fslr_choose_representatives', 'fslr_cluster_timings']
+            'fslr_choose_representatives', 'fslr_cluster_timings',
+            'fslr_match_reads', 'fslr_match_rows', 'fslr_match_timings']
 # fslr_score_pairs' flag bits (include/fslr_hip.h)
 SCORE_GATE, SCORE_EDGE, SCORE_ZD_GATE, SCORE_ZD_OVERLAP = 1, 2, 4, 8
 # fslr_coverage_*: keys per tile of the sorted arrays, queries per chunk (include/fslr_hip.h)
 COVERAGE_TILE = 256
 COVERAGE_CHUNK = 1 << 21
+# fslr_match_reads: distinct partners of one query read held in on-chip memory (include/fslr_hip.h FSLR_MATCH_SET)
+MATCH_SET = 256
 
 
 class HipUnavailable(RuntimeError):
@@ -81,6 +84,12 @@ class RowsInfo(ctypes.Structure):
 
     def as_dict(self):
         return {f: int(getattr(self, f)) for f, _ in self._fields_ if f != 'pad'}
+
+
+class MatchQueries(ctypes.Structure):
+    _fields_ = [('n_reads', ctypes.c_int64), ('n_intervals', ctypes.c_int64)] + [
+        (f, ctypes.c_void_p) for f in ('read_off', 'read_qlen2', 'read_nal', 'iv_chrom', 'iv_start', 'iv_end',
+                                       'iv_thr', 'exclude')]
 
 
 class Params(ctypes.Structure):
@@ -225,6 +234,10 @@ def load(path: str = LIB_PATH):
         'fslr_search_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         'fslr_score_pairs': (ctypes.c_int, [vp, ctypes.POINTER(Params), i64, vp, vp, vp, vp, vp]),
         'fslr_score_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        'fslr_match_reads': (ctypes.c_int, [vp, ctypes.POINTER(Params), ctypes.POINTER(MatchQueries), ctypes.c_uint32,
+                                            vp, vp, vp, ctypes.POINTER(ctypes.c_int64)]),
+        'fslr_match_rows': (ctypes.c_int, [vp, vp, vp, vp, vp, i64]),
+        'fslr_match_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         'fslr_coverage_build': (ctypes.c_int, [vp, i64, i32, vp, vp, vp]),
         'fslr_coverage_at': (ctypes.c_int, [vp, i64, vp, vp, vp]),
         'fslr_coverage_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
@@ -899,6 +912,52 @@ class Context:
         ms = (ctypes.c_float * 3)()
         self._check(self._L.fslr_score_timings(self._h, ms))
         return dict(zip(('upload', 'kernel', 'download'), (float(x) for x in ms)))
+
+    # -- new reads against the resident index (fslr_hip.h fslr_match_reads / fslr_match_rows) --------
+    def match_reads(self, read_off, read_qlen2, read_nal, iv_chrom, iv_start, iv_end, iv_thr, qlen_cut, nal_cut,
+                    pass_table, emit_mask=SCORE_EDGE, exclude=None):
+        """The pair loop for query reads outside the uploaded set (a CSR like set_reads', dense chromosome
+        ids, folded thresholds): ``(offsets int64[n + 1], counts int32[n, 3], best int32[n])``, counts =
+        candidates, gated, edges per query read, best = the partner of the largest I / U or -1.  The rows
+        (``offsets[-1]`` of them) are fetched with ``match_rows``."""
+        off, q2, nal, ch, st, en, th = (np.ascontiguousarray(x, dtype=np.int32) for x in
+                                        (read_off, read_qlen2, read_nal, iv_chrom, iv_start, iv_end, iv_thr))
+        if off.ndim != 1 or off.size < 1:
+            raise ValueError('read_off must be one-dimensional with n_reads + 1 entries')
+        n = off.size - 1
+        if not (q2.shape == nal.shape == (n,)):
+            raise ValueError('read_qlen2 and read_nal must have one entry per query read')
+        if not (ch.ndim == 1 and ch.shape == st.shape == en.shape == th.shape):
+            raise ValueError('iv_chrom, iv_start, iv_end and iv_thr must be one-dimensional and of one length')
+        ex = None
+        if exclude is not None:
+            ex = np.ascontiguousarray(exclude, dtype=np.int32)
+            if ex.shape != (n,):
+                raise ValueError('exclude must have one entry per query read')
+        q = MatchQueries(n, int(ch.size), *(_ptr(a) for a in (off, q2, nal, ch, st, en, th)),
+                         _ptr(ex) if ex is not None else None)
+        p = self._params(qlen_cut, nal_cut, pass_table, 0)
+        offsets, counts, best = np.zeros(n + 1, np.int64), np.zeros((n, 3), np.int32), np.full(n, -1, np.int32)
+        total = ctypes.c_int64(0)
+        self._check(self._L.fslr_match_reads(self._h, ctypes.byref(p), ctypes.byref(q), int(emit_mask), _ptr(offsets),
+                                             _ptr(counts), _ptr(best), ctypes.byref(total)))
+        self._match_rows = int(total.value)
+        return offsets, counts, best
+
+    def match_rows(self):
+        """The last match_reads' rows: ``(partner int32, I int32, U int32, flags uint8)``, query read after
+        query read in candidate (first-visit) order."""
+        n = getattr(self, '_match_rows', 0)
+        partner, I, U = (np.zeros(n, np.int32) for _ in range(3))
+        flags = np.zeros(n, np.uint8)
+        self._check(self._L.fslr_match_rows(self._h, _ptr(partner), _ptr(I), _ptr(U), _ptr(flags), n))
+        return partner, I, U, flags
+
+    def match_timings(self) -> dict:
+        """HIP-event times (ms) of the last match_reads (profiling contexts), summed over its chunks."""
+        ms = (ctypes.c_float * 4)()
+        self._check(self._L.fslr_match_timings(self._h, ms))
+        return dict(zip(('upload', 'search', 'score', 'download'), (float(x) for x in ms)))
 
     # -- read depth at query points (fslr_hip.h fslr_coverage_build / fslr_coverage_at) --------------
     def coverage_build(self, chrom, rstart, rend, n_chroms):

@@ -442,6 +442,65 @@ class PairScores:
                              'jaccard_similarity': self.jaccard, 'n_i': self.I, 'gate': self.gate, 'edge': self.edge})
 
 
+class ReadMatches:
+    """DeviceIntervalIndex.match_reads' result.  Query read q's rows are ``offsets[q]:offsets[q + 1]`` of
+    ``partner`` (resident read ranks), ``I``, ``U`` and ``flags`` (fslr_hip.h FSLR_SCORE_*), in the order the
+    reference's loop first meets the partners.  ``counts[q]`` = (candidates, gated, edges) over every candidate
+    whatever was emitted; ``best[q]`` = the partner of the edge with the largest I / U (the earlier on ties),
+    -1 without an edge.  ``query_names[q]`` names the query reads, ``qnames_by_rank`` the resident ones."""
+
+    def __init__(self, offsets, partner, I, U, flags, counts, best, query_names, qnames_by_rank):
+        self.offsets, self.partner, self.I, self.U, self.flags = offsets, partner, I, U, flags
+        self.counts, self.best = counts, best
+        self.query_names, self.qnames_by_rank = query_names, qnames_by_rank
+
+    def __len__(self):
+        return int(self.offsets.shape[0] - 1)
+
+    def query_of_row(self) -> np.ndarray:
+        """The query read (its index) of every row."""
+        return np.repeat(np.arange(len(self), dtype=np.int64), np.diff(self.offsets))
+
+    def to_frame(self):
+        """One row per emitted pair: ``query`` (the new read), ``qname`` (the resident partner),
+        ``jaccard_similarity`` (I / U as a Python float would be, 0.0 where U == 0), ``n_intersections``."""
+        n = int(self.partner.shape[0])
+        j = np.divide(self.I, self.U, out=np.zeros(n, np.float64), where=self.U != 0)
+        names = np.asarray(self.query_names, dtype=object)
+        return pd.DataFrame({'query': names[self.query_of_row()] if n else np.zeros(0, object),
+                             'qname': self.qnames_by_rank[self.partner] if n else np.zeros(0, object),
+                             'jaccard_similarity': j, 'n_intersections': self.I})
+
+    def clusters(self, table_or_labels):
+        """The resident components each query read's EDGE rows touch: ``(offsets int64[n + 1], labels
+        int64[total], join int64[n])``.  ``labels[offsets[q]:offsets[q + 1]]`` are the distinct min-rank
+        component labels among q's EDGE partners in first-visit order; ``join[q]`` is the label q would
+        join (the smallest), -1 when q has no edge.  ``table_or_labels``: a ClusterTable, a graph with
+        ``labels``, or the min-rank label vector itself.  Host numpy, one sort of the edge rows."""
+        if isinstance(table_or_labels, ClusterTable):
+            t = table_or_labels
+            lab_of = np.where(t.cid >= 0, t.roots[np.maximum(t.cid, 0)] if t.n_clusters else 0,
+                              np.arange(t.cid.shape[0])).astype(np.int64)
+        else:
+            lab_of = _labels_of(table_or_labels).astype(np.int64)
+        n = len(self)
+        rows = np.flatnonzero(self.flags & SCORE_EDGE)
+        q = self.query_of_row()[rows]
+        lab = lab_of[self.partner[rows]] if rows.size else np.zeros(0, np.int64)
+        # the first row of every distinct (query, label): np.unique's first indices, back in row order
+        _, first = np.unique(q * np.int64(max(lab_of.shape[0], 1)) + lab, return_index=True)
+        first.sort()
+        q, lab = q[first], lab[first]
+        off = np.zeros(n + 1, np.int64)
+        np.cumsum(np.bincount(q, minlength=n), out=off[1:])
+        join = np.full(n, -1, np.int64)
+        if q.size:
+            lo = np.full(n, np.iinfo(np.int64).max)
+            np.minimum.at(lo, q, lab)
+            join = np.where(off[1:] > off[:-1], lo, -1)
+        return off, lab, join
+
+
 # ------------------------------------------------------------------ device stages
 class DeviceIntervalIndex:
     """What build_interval_trees returns: the CSR in HBM plus the sorted interval index."""
@@ -583,6 +642,73 @@ class DeviceIntervalIndex:
                 raise ZeroDivisionError(f'division by zero (pair {k}: {qn[a[k]]!r}, {qn[b[k]]!r})')
         return PairScores(a, b, I, U, flags, qn)
 
+    # -- new reads against the resident index (cluster.py:197-222 with an external list1) -----------
+    _EMIT = {'edges': SCORE_EDGE, 'gated': SCORE_GATE, 'all': 0}
+
+    def match_reads(self, reads, overlap_cutoff, jaccard_threshold, qlen_diff, diff, emit='edges',
+                    exclude=None) -> ReadMatches:
+        """What the reference's pair loop would do for reads that are not in this index: per new read its
+        candidate partners in first-visit order and, per partner, score_pairs' I, U and flags for (list1 =
+        the new read, list2 = the partner).  The edge cap is not applied.  One device call
+        (fslr_match_reads); the query state of the index is left alone.
+
+        ``reads``: an IntervalData or a list of IntervalItem (the new reads' `data` list: reads rank by first
+        appearance, a read's intervals keep list order, chromosomes are the values this index was built
+        with), or a ``prep.CSR`` whose ``iv_chrom`` already holds this index's dense ids.  ``emit``: the
+        rows to return: 'edges', 'gated' (the length gate passed) or 'all' candidates.  ``exclude``: per
+        new read a resident rank (or qname) to skip, -1 / None for none."""
+        min(jaccard_threshold)                              # cluster.py:188 raises on an empty list
+        if emit not in self._EMIT:
+            raise ValueError(f"emit must be 'edges', 'gated' or 'all', not {emit!r}")
+        if self.long is not None:
+            raise NotImplementedError(f'match_reads does not take an index with reads of more than {FSLR_MAX_L} '
+                                      f'intervals')
+        if isinstance(reads, CSR):
+            qcsr, chrom = reads, np.asarray(reads.iv_chrom, np.int32)
+            names = np.arange(qcsr.n_reads)
+        else:
+            raw = None
+            if not isinstance(reads, IntervalData):
+                reads = list(reads)
+                raw = np.asarray([it[0] for it in reads])
+                reads = IntervalData.from_items(reads)
+            qcsr = reads.csr()
+            raw = np.asarray(reads.chrom) if raw is None else raw
+            chrom = self._dense_chroms(raw[np.asarray(qcsr.data_pos, np.int64)]) if len(reads) else \
+                np.zeros(0, np.int32)
+            names = reads.qnames[qcsr.read_qcode]
+        if has_long_reads(qcsr):
+            r = int(np.argmax(np.diff(qcsr.read_off) > FSLR_MAX_L))
+            raise ValueError(f'query read {r} has more than {FSLR_MAX_L} intervals')
+        n = qcsr.n_reads
+        ex = None
+        if exclude is not None:
+            e = np.asarray(exclude)
+            if e.shape != (n,):
+                raise ValueError('exclude must have one entry per query read')
+            if e.dtype.kind in 'iu':
+                if e.size and (e.min() < -1 or e.max() >= self.csr.n_reads):
+                    raise IndexError(f'exclude: a value is neither -1 nor a read rank in [0, {self.csr.n_reads})')
+                ex = e.astype(np.int32)
+            else:
+                ex = np.full(n, -1, np.int32)
+                has = np.asarray([v is not None for v in e.tolist()], bool)
+                ex[has] = self._ranks(e[has])
+        ctx = self.ctx
+        if isinstance(self, RowsIndex):
+            if self.overlap != float(overlap_cutoff):            # folded on the device at the upload
+                ctx.fold_thresholds(overlap_cutoff)
+                self.overlap = float(overlap_cutoff)
+        elif self.__dict__.get('_thr_key') != (float(overlap_cutoff), getattr(ctx, 'thr_gen', 0)):
+            ctx.set_thresholds(fold_overlap_threshold(self.csr.iv_aln, overlap_cutoff))
+            self._thr_key = (float(overlap_cutoff), ctx.thr_gen)
+        off, counts, best = ctx.match_reads(qcsr.read_off, qcsr.read_qlen2, qcsr.read_nal, chrom, qcsr.iv_start,
+                                            qcsr.iv_end, fold_overlap_threshold(qcsr.iv_aln, overlap_cutoff),
+                                            1 - qlen_diff, 1 - diff, pass_table(jaccard_threshold),
+                                            self._EMIT[emit], ex)
+        partner, I, U, flags = ctx.match_rows()
+        return ReadMatches(off, partner, I, U, flags, counts, best, names, self.data.qnames[self.csr.read_qcode])
+
     def __getitem__(self, chrom):
         return ChromosomeView(self, chrom)
 
@@ -686,6 +812,10 @@ class MultiGpuIndex:
     def score_pairs(self, *args, **kwargs):
         raise NotImplementedError('a multi-GPU index lives in the rank processes and cannot score pairs from here; '
                                   'build it with n_gpus=1 to score pairs')
+
+    def match_reads(self, *args, **kwargs):
+        raise NotImplementedError('a multi-GPU index lives in the rank processes and cannot match reads from here; '
+                                  'build it with n_gpus=1 to match reads')
 
 
 def _open_context(device: int | None = None) -> Context:

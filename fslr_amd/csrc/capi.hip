@@ -181,6 +181,7 @@ void fslr_ctx_destroy(fslr_ctx* c) {
   fslr_score_free(c);
   fslr_coverage_free(c);
   fslr_cluster_free(c);
+  fslr_match_free(c);
   if (c->ev_ok) {
     for (auto& e : c->ev) (void)hipEventDestroy(e);
     for (auto& e : c->kev) (void)hipEventDestroy(e);

@@ -180,6 +180,7 @@ struct fslr_ctx {
   uint64_t index_gen = 0;                // bumped by every fslr_build_index (a saved search batch belongs to one)
   struct ScoreWork* scw = nullptr;       // fslr_score_pairs' scratch and its last call's times (score.hip)
   struct CoverageWork* cvw = nullptr;    // fslr_coverage_build's resident keys, the chunk staging (coverage.hip)
+  struct MatchWork* mtw = nullptr;       // fslr_match_reads' block and chunk scratch, its last batch's rows (match.hip)
   struct ClusterWork* clw = nullptr;     // fslr_cluster_table's resident table, the assign / representatives scratch (clusters.hip)
   // reads of more than FSLR_MAX_L intervals (long.hip): the virtual-read map and the long-pair stage
   bool lg_set = false;
@@ -234,6 +235,8 @@ void fslr_score_free(fslr_ctx* c);
 void fslr_coverage_free(fslr_ctx* c);
 // frees the resident cluster table and its scratch (clusters.hip)
 void fslr_cluster_free(fslr_ctx* c);
+// frees the read matching's buffers and its saved batch (match.hip)
+void fslr_match_free(fslr_ctx* c);
 
 namespace fslr {
 

@@ -65,6 +65,10 @@
  *   fslr_choose_representatives
  *                         cluster.py:237-254 choose_alignment: per cluster the qname with the highest mean
  *                         alignment_score, the first in frame order on ties (idxmax)
+ *   fslr_match_reads,
+ *   fslr_match_rows       cluster.py:197-222 the pair loop for query reads that are not in the uploaded set:
+ *                         the search (:201), the seen-set (:205-208) and the pair predicates (:209-219)
+ *                         against the resident index, without the edge cap (:223-224)
  *
  * Conventions: plain C types, caller-owned host arrays, library-owned device
  * memory behind an opaque context.  Every function returns FSLR_OK (0) or an
@@ -675,6 +679,66 @@ int  fslr_choose_representatives(fslr_ctx *ctx, int64_t n_codes, const int64_t *
                                  const int64_t *score_cnt, const int64_t *first_row, int64_t n_out, double *avg,
                                  int64_t *winner_code);
 int  fslr_cluster_timings(fslr_ctx *ctx, float *ms);
+
+/* Match reads that are NOT in the uploaded set against the resident index: for a query read Q, given
+ * like a row of fslr_reads (its intervals in the order its loop walks them, dense chromosome ids of the
+ * uploaded CSR, folded iv_thr, its qlen2 and n_alignments), what the reference's pair loop
+ * (cluster.py:197-222) does with query_key = Q and list1 = Q's intervals.
+ *   Candidates  for each interval of Q in order, the hits of fslr_search's contract (its hit rule and
+ *               its order) on the built index; the candidates of Q are the distinct resident reads of
+ *               those hits in the order the loop first meets them (the seen-set of :205-208, kept per
+ *               query read).  exclude[q] (a resident rank, or -1) is skipped entirely, as
+ *               `o_data.qname == query_key` (:203) is: it lets a caller ask about a resident read.  A
+ *               query read of 0 intervals has no candidates; an interval whose chromosome id lies
+ *               outside [0, n_chroms) has no hits.
+ *   Per candidate P   flags, I and U are exactly fslr_score_pairs' for the ordered pair (list1 = Q,
+ *               list2 = P): the gate from Q's and P's qlen2 and n_alignments, first-fit under Q's and
+ *               P's thresholds (the resident ones are those currently set), EDGE from pass_table,
+ *               ZD_OVERLAP gives I = U = 0.  ZeroDivisionError is only flagged, never returned.
+ *   Rows        (partner rank, I, U, flags) for a candidate iff emit_mask == 0 (every candidate) or
+ *               flags & emit_mask != 0, in candidate (first-visit) order per query read.  The first-fit
+ *               of a candidate that cannot be emitted is skipped.  The same bytes on every run.
+ *   Per query read, whatever emit_mask: counts[3 q ..] = candidates, candidates with GATE, candidates
+ *               with EDGE; best[q] = the EDGE candidate with the largest I / U (compared exactly,
+ *               I1 U2 against I2 U1; ties to the earlier candidate), -1 without an edge.
+ * fslr_match_reads: row_off (NULL, or [n_reads + 1]) gets the exclusive prefix of the row counts,
+ * *n_rows (may be NULL) their total; counts and best may be NULL.  fslr_match_rows then writes the last
+ * fslr_match_reads' rows, query read after query read.  capacity < n_rows: FSLR_ERR_INVALID, nothing is
+ * written.  n_reads == 0 is valid.  The saved batch belongs to the reads and the index build it was made
+ * on: after another fslr_set_reads* or fslr_build_index, fslr_match_rows returns FSLR_ERR_STATE until the
+ * next fslr_match_reads.
+ * FSLR_ERR_STATE where fslr_search gives it: no index built, a chromosome or position filter active, or
+ * n_shards > 1.  FSLR_ERR_INVALID: the context holds virtual reads (as fslr_score_pairs), a query read of
+ * more than FSLR_MAX_L intervals, read_off not non-decreasing, or an exclude value that is neither -1 nor
+ * a resident rank (the message names the first offender; nothing is computed).  From params the call
+ * uses qlen_cut, nal_cut and pass_table.  Host pointers; syncs.  The query state (edges, labels, degrees,
+ * the cap), the saved search batch, the score scratch, the coverage set and the cluster table are left
+ * alone.  The query reads go up in bounded blocks and are evaluated in chunks of a bounded number of
+ * hits (at least one read: a read's hits are staged whole): no scratch grows with the batch.
+ * FSLR_MATCH_SET: the distinct partners of one query read held in on-chip memory; a read with more is
+ * still exact (its later hits are deduplicated against the staged hit list) but slower.
+ * Out of scope: the edge cap (:223-224; a matched read's loop is not part of the resident graph's cap
+ * replay, so every candidate is evaluated), query or resident reads of more than FSLR_MAX_L intervals,
+ * matching through the multi-GPU split, and inserting matched reads into the index.
+ * fslr_match_timings (fslr_set_profiling 1 or 2): HIP-event times (ms) of the last fslr_match_reads,
+ * ms[0..3] = upload, search (count + fill), dedupe + score (+ row compaction), download, summed over its
+ * blocks and chunks. */
+#define FSLR_MATCH_SET 256
+typedef struct {
+    int64_t n_reads, n_intervals;
+    const int32_t *read_off;       /* [n_reads+1] */
+    const int32_t *read_qlen2;     /* [n_reads] */
+    const int32_t *read_nal;       /* [n_reads] */
+    const int32_t *iv_chrom;       /* [n_intervals] dense ids of the uploaded CSR */
+    const int32_t *iv_start;
+    const int32_t *iv_end;
+    const int32_t *iv_thr;         /* folded overlap threshold, as fslr_reads */
+    const int32_t *exclude;        /* NULL, or [n_reads]: a resident rank to skip, or -1 */
+} fslr_match_queries;
+int  fslr_match_reads(fslr_ctx *ctx, const fslr_params *params, const fslr_match_queries *queries, uint32_t emit_mask,
+                      int64_t *row_off, int32_t *counts, int32_t *best, int64_t *n_rows);
+int  fslr_match_rows(fslr_ctx *ctx, int32_t *partner, int32_t *I, int32_t *U, uint8_t *flags, int64_t capacity);
+int  fslr_match_timings(fslr_ctx *ctx, float *ms);
 
 /* Device-side views for collectives (e.g. RCCL all_gather of labels). */
 int  fslr_labels_device_ptr(fslr_ctx *ctx, void **dptr);
