@@ -20,6 +20,7 @@
 //      SURVEY.md §8a A6) are exactly: q+1 .. q+n_fwd, plus p in [bwd_begin, q) with end_p >= start_q.
 #include <hipcub/hipcub.hpp>
 
+#include "idxsearch.hpp"   // kTile, kGroup: the tile prefix as the searches read it
 #include "kernels.hpp"
 #include "wave.hpp"
 
@@ -28,8 +29,7 @@ namespace {
 
 constexpr int kRangeBlock = 256;        // threads of k_ranges
 constexpr int kRangeSpan = 1024;        // sorted positions per k_ranges block (4 per thread)
-constexpr int kTile = 256;              // pmax tiles (window edges are tile-aligned)
-constexpr int kWin = 512;
+constexpr int kWin = 512;               // (window edges are aligned to the kTile pmax tiles)
 constexpr int kLeanHalo = kWin;         // forward halo of the lean k_ranges; a window beyond it gallops
 
 __global__ void k_keys_csr(const int4* __restrict__ rmeta, const int4* __restrict__ iv, int n,
@@ -329,8 +329,7 @@ __global__ __launch_bounds__(kTile) void k_tile_max(const unsigned long long* __
 
 // inclusive max-scan of the tile maxima in two levels: groups of 1024 tiles (one block each,
 // coalesced) hold local inclusive prefixes and a group total; one block scans the group totals.
-// The inclusive prefix of tile t is max(group_excl[t / 1024], tile_loc[t]).
-constexpr int kGroup = 1024;
+// The inclusive prefix of tile t is max(group_excl[t / kGroup], tile_loc[t]).
 
 __global__ __launch_bounds__(kGroup) void k_tile_scan_local(const unsigned long long* __restrict__ tile_max, int nt,
                                                             unsigned long long* __restrict__ tile_loc,

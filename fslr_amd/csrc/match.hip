@@ -17,18 +17,21 @@
 // below only by the largest single read's hits).  No scratch grows with the batch.
 //   count   one wavefront per query read: one lane per interval finds its span [lo, hi) (the upper
 //           bound of qe in the chromosome's starts; the first tile whose prefix max of (chrom, end)
-//           reaches (c, qs), search.hip), then the wave counts each span's hits 64 positions at a time
+//           reaches (c, qs): IndexView::span_of of idxsearch.hpp, search.hip's span pass too), then the
+//           wave counts each span's hits 64 positions at a time
 //   fill    one wavefront per read of the chunk: a hit's rank in its interval's list is its ascending
-//           rank, re-ranked inside a run of equal start on (end descending, data position ascending),
-//           written top-down: the read's hit list in visiting order, as partner ranks
+//           rank, re-ranked inside a run of equal start on (end descending, data position ascending:
+//           IndexView::tie_shift), written top-down: the read's hit list in visiting order, as
+//           partner ranks
 //   score   one wavefront per read: Q's intervals staged in LDS; the hit list 64 at a time through a
 //           per-wave LDS hash set (kMatchSetCap = FSLR_MATCH_SET distinct partners; a slot keeps the
 //           smallest hit index that claimed it, so the first visits of a batch come out in lane order).
 //           Once the set holds kMatchSetCap partners it is closed, and a later hit whose partner it lacks
 //           is a first visit iff no earlier hit of the staged list past the closing point names the same
 //           partner (the witness rule, on the list).  The batch's new partners are scored four (two,
-//           one) at a time on 16- (32-, 64-)lane groups: score.hip's first-fit with list1's rows read
-//           from LDS.  Emitted rows are staged at the read's hit offset (rows <= hits).
+//           one) at a time on 16- (32-, 64-)lane groups: the first-fit of firstfit.hpp, score.hip's
+//           too, with list1's rows read from LDS.  Emitted rows are staged at the read's hit offset
+//           (rows <= hits).
 //   compact exclusive scan of the chunk's row counts, rows copied dense, then D2H
 // Every output slot is a function of the input alone: no global atomics, the same bytes on every run.
 // Algorithmic bytes: count 8 B per span position; fill 16 B per span position + 4 B per hit; score 4 B
@@ -42,7 +45,9 @@
 #include <vector>
 
 #include "ctx.hpp"
+#include "firstfit.hpp"
 #include "fslr_hip.h"
+#include "idxsearch.hpp"
 #include "kernels.hpp"
 #include "wave.hpp"
 
@@ -50,15 +55,12 @@ using namespace fslr;
 
 namespace {
 
-constexpr int kTile = 256;                     // index.hip: pmax tiles
-constexpr int kGroup = 1024;                   // index.hip: tiles per scan group
 constexpr int kMatchSetCap = FSLR_MATCH_SET;   // distinct partners the LDS set takes before it closes
 constexpr int kSetSlots = 512;                 // open addressing; at most kMatchSetCap + 63 keys
 constexpr int kWavesPerBlock = 4;
 constexpr int64_t kBlockReads = int64_t(1) << 16;
 constexpr int64_t kBlockIvs = int64_t(1) << 20;
 constexpr int64_t kBudget = int64_t(1) << 21;  // hits per chunk: 40 MiB of hit / row scratch
-constexpr int kPassBytes = FSLR_MAX_L * kPassStride;
 static_assert(kMatchSetCap + kWave <= kSetSlots * 3 / 4, "the set's table must stay sparse");
 
 }  // namespace
@@ -110,31 +112,6 @@ void fslr_match_free(fslr_ctx* c) {
 
 namespace {
 
-// the built index as the search reads it (search.hip)
-struct IndexView {
-  const int2* crange;
-  const int* s_start;
-  const unsigned long long* endkey;
-  const unsigned long long* loc;         // index.hip's tile prefix: local group prefixes
-  const unsigned long long* group_excl;  // and the exclusive group prefixes
-  const int4* idx4;
-  const int4* rmeta;
-  const int* data_pos;                   // null: the data position is the CSR index
-  int nt, ni, n, n_chroms;
-  __device__ __forceinline__ unsigned long long incl(int t) const {
-    FSLR_BOUND(t, nt);
-    const unsigned long long a = group_excl[t / kGroup], b = loc[t];
-    return a > b ? a : b;
-  }
-  // the data position of the stored interval with tag read << 6 | j
-  __device__ __forceinline__ int dpos(int tag) const {
-    FSLR_BOUND(tag >> 6, n);
-    const int k = rmeta[tag >> 6].x + (tag & 63);
-    FSLR_BOUND(k, ni);
-    return data_pos ? data_pos[k] : k;
-  }
-};
-
 struct MatchArgs {
   IndexView ix;
   const int* roffq;                      // the block's read_off (as the caller's: absolute), qlen2, nal, exclude
@@ -161,39 +138,6 @@ struct MatchArgs {
   long long* nrows;                      // chunk-relative
 };
 
-// [lo, hi) of query (c, qs, qe): search.hip's span pass for one query
-__device__ __forceinline__ int2 span_of(const IndexView& ix, int c, int qs, int qe) {
-  int lo = 0, hi = 0;
-  if (c >= 0 && c < ix.n_chroms) {
-    const int2 cr = ix.crange[c];
-    int a = cr.x, z = cr.y;                        // first position of the chromosome with start > qe
-    while (a < z) {
-      const int mid = (a + z) >> 1;
-      FSLR_BOUND(mid, ix.ni);
-      if (ix.s_start[mid] <= qe) a = mid + 1; else z = mid;
-    }
-    lo = hi = a;
-    if (hi > cr.x) {
-      const unsigned long long key = (static_cast<unsigned long long>(c) << 32) | static_cast<unsigned>(qs);
-      int tb = cr.x / kTile, te = (hi - 1) / kTile;
-      if (ix.incl(te) >= key) {
-        while (tb < te) {
-          const int mid = (tb + te) >> 1;
-          if (ix.incl(mid) >= key) te = mid; else tb = mid + 1;
-        }
-        int p = max(tb * kTile, cr.x);
-        const int pe = min((tb + 1) * kTile, hi);
-        for (; p < pe; ++p) {
-          FSLR_BOUND(p, ix.ni);
-          if (static_cast<int>(static_cast<unsigned>(ix.endkey[p])) >= qs) break;
-        }
-        lo = p;
-      }
-    }
-  }
-  return make_int2(lo, hi);
-}
-
 __global__ __launch_bounds__(256) void k_match_count(MatchArgs s) {
   const int lane = threadIdx.x & 63;
   const int nw = gridDim.x * (blockDim.x >> 6);
@@ -204,7 +148,7 @@ __global__ __launch_bounds__(256) void k_match_count(MatchArgs s) {
     if (lane < L) {
       FSLR_BOUND(o0 + lane, s.nbi);
       qs = max(s.qs[o0 + lane], 0);                // stored ends are >= 0: the same hits
-      sp = span_of(s.ix, s.qc[o0 + lane], qs, s.qe[o0 + lane]);
+      sp = s.ix.span_of(s.qc[o0 + lane], qs, s.qe[o0 + lane]);
       s.span[o0 + lane] = sp;
     }
     long long tot = 0;
@@ -214,12 +158,7 @@ __global__ __launch_bounds__(256) void k_match_count(MatchArgs s) {
       int cnt = 0;
       for (int p0 = lo; p0 < hi; p0 += kWave) {
         const int p = p0 + lane;
-        bool hit = false;
-        if (p < hi) {
-          FSLR_BOUND(p, s.ix.ni);
-          hit = static_cast<int>(static_cast<unsigned>(s.ix.endkey[p])) >= q;
-        }
-        cnt += __popcll(__ballot(hit));
+        cnt += __popcll(__ballot(p < hi && s.ix.reaches(p, q)));
       }
       if (lane == i) mine = cnt;
       tot += cnt;
@@ -254,24 +193,8 @@ __global__ __launch_bounds__(256) void k_match_fill(MatchArgs s) {
         const unsigned long long hm = __ballot(hit);
         if (hit) {
           int rk = asc + mbcnt(hm);                // ascending rank among the interval's hits, ties in index order
-          const bool tied = (p > sp.x && ix.s_start[p - 1] == rec.x) || (p + 1 < sp.y && ix.s_start[p + 1] == rec.x);
-          if (tied) {
-            // the run of equal start inside the span: the hits of it before p leave the rank, those that
-            // precede p in (end descending, data position ascending) enter it (search.hip's fill)
-            const int me = ix.dpos(rec.w);
-            int rb = p;
-            while (rb > sp.x && ix.s_start[rb - 1] == rec.x) --rb;
-            int before = 0, first = 0;
-            for (int f = rb; f < sp.y; ++f) {
-              FSLR_BOUND(f, ix.ni);
-              const int4 rf = ix.idx4[f];
-              if (rf.x != rec.x) break;
-              if (rf.y < qs || f == p) continue;
-              before += f < p;
-              first += rf.y > rec.y || (rf.y == rec.y && ix.dpos(rf.w) < me);
-            }
-            rk += first - before;
-          }
+          // (its data position is looked up for a tied hit only)
+          if (ix.tied(sp, p, rec.x)) rk += ix.tie_shift<false>(sp, p, rec, qs, ix.ids<false>(rec.w).y);
           const long long dst = base + cnt - 1 - rk;   // top-down
           FSLR_BOUND(dst, s.h_cap);
           s.hits[dst] = static_cast<int>(static_cast<unsigned>(rec.w) >> 6);
@@ -283,54 +206,24 @@ __global__ __launch_bounds__(256) void k_match_fill(MatchArgs s) {
   }
 }
 
-// 64 / W candidates side by side, candidate k on the W-lane group of this lane: score.hip's first-fit with
-// list1 = the query read's LA rows in LDS (uniform over the wave), list2's columns on the group's lanes
+// 64 / W candidates side by side, candidate k on the W-lane group of this lane: the first-fit of firstfit.hpp
+// with list1 = the query read's LA rows in LDS (uniform over the wave), list2's columns on the group's lanes
 template <int W>
 __device__ __forceinline__ void match_groups(const MatchArgs& s, const int4* qiv, int LA, int k, bool valid, int offB,
                                              int LB, int gate, int lane, unsigned* res) {
   const int l = lane & (W - 1);
-  const int gbase = lane & ~(W - 1);
   const bool col = valid && l < LB;
   int4 bj = make_int4(-2, 0, 0, 0);
   if (col) {
     FSLR_BOUND(offB + l, s.ix.ni);
     bj = s.iv[offB + l];
   }
-  bool used = false, zd = false;
-  int I = 0;
+  FirstFit ff;
   for (int i = 0; i < LA; ++i) {
     const int4 a = qiv[i];
-    const bool cand = col && !zd && !used && bj.x == a.x;
-    // FSLR_THR_ZERO_ALN is a sentinel thr_ok would accept: tested before iv_match_general
-    const bool zero = cand && (a.w == FSLR_THR_ZERO_ALN || bj.w == FSLR_THR_ZERO_ALN);
-    const bool hit = cand && (zero || iv_match_general(a.y, a.z, a.w, bj.y, bj.z, bj.w));
-    unsigned long long hm = __ballot(hit), zm = __ballot(zero);
-    if constexpr (W < kWave) {
-      hm = (hm >> gbase) & ((1ull << W) - 1);
-      zm >>= gbase;
-    }
-    if (hm) {
-      const int j = __builtin_ctzll(hm);
-      if ((zm >> j) & 1ull) {
-        zd = true;                     // the row's walk meets the aln_size == 0 column before any match
-      } else {
-        used |= l == j;
-        ++I;
-      }
-    }
+    ff.row<W>(a.x, a.y, a.z, a.w, true, bj, col, lane);
   }
-  if (valid && l == 0) {
-    int U = LA + LB - I, flags = gate;
-    if (zd) {
-      I = U = 0;
-      flags |= FSLR_SCORE_ZD_OVERLAP;
-    } else if ((flags & FSLR_SCORE_GATE) && I > 0) {
-      const int t = (I - 1) * kPassStride + (U - 1);
-      FSLR_BOUND(t, kPassBytes);
-      if (s.pt[t]) flags |= FSLR_SCORE_EDGE;
-    }
-    res[k] = static_cast<unsigned>(I) | (static_cast<unsigned>(U) << 8) | (static_cast<unsigned>(flags) << 16);
-  }
+  if (valid && l == 0) res[k] = fit_result(LA, LB, ff.I, ff.zd, gate, s.pt);
 }
 
 struct CandMeta {
@@ -348,9 +241,7 @@ __device__ __forceinline__ CandMeta cand_meta(const MatchArgs& s, const int* can
     const int4 mb = s.ix.rmeta[p];
     m.offB = mb.x;
     m.LB = mb.y & 0xffff;
-    bool zd = false;
-    const bool pass = lengths_pass(q2, mb.z, qn, mb.w, s.qcut, s.ncut, &zd);
-    m.gate = zd ? FSLR_SCORE_ZD_GATE : pass ? FSLR_SCORE_GATE : 0;
+    m.gate = gate_flags(q2, mb.z, qn, mb.w, s.qcut, s.ncut);
     // a candidate with the gate clear can carry ZD_GATE and ZD_OVERLAP only: where the mask asks for neither
     // that it has nor for ZD_OVERLAP, no row can come of it and its first-fit is skipped
     m.score = (m.gate & FSLR_SCORE_GATE) || s.emit_mask == 0 || (s.emit_mask & FSLR_SCORE_ZD_OVERLAP) ||
@@ -525,8 +416,6 @@ __global__ __launch_bounds__(256) void k_match_compact(const long long* __restri
   }
 }
 
-int wave_grid(long long waves) { return grid_for(waves, kWavesPerBlock, 256 * 32); }
-
 int ensure_block(fslr_ctx* c, MatchWork* w) {
   if (w->block_ok) return FSLR_OK;
   int rc;
@@ -560,15 +449,10 @@ int ensure_hits(fslr_ctx* c, MatchWork* w, int64_t need) {
 
 // why this context cannot match (where fslr_search and fslr_score_pairs could not answer), or FSLR_OK
 int match_state(fslr_ctx* c, const char* who) {
-  const std::string f = std::string(who) + ": ";
-  if (!c->index_built) return fail(c, FSLR_ERR_STATE, f + "fslr_build_index first");
-  if (c->filter_active)
-    return fail(c, FSLR_ERR_STATE, f + "a chromosome or position filter is active (the index is partial)");
-  if (c->n_shards > 1 || c->built_n_shards > 1)
-    return fail(c, FSLR_ERR_STATE, f + "the index was built for one of several shards (it is partial)");
+  if (int rc = search_state(c, who)) return rc;
   if (c->lg_set)
-    return fail(c, FSLR_ERR_INVALID, f + "the context holds reads of more than " + std::to_string(FSLR_MAX_L) +
-                                         " intervals (virtual reads), which it does not match against");
+    return fail(c, FSLR_ERR_INVALID, std::string(who) + ": the context holds reads of more than " +
+                                         std::to_string(FSLR_MAX_L) + " intervals (virtual reads), which it does not match against");
   return FSLR_OK;
 }
 
@@ -634,10 +518,8 @@ int fslr_match_reads(fslr_ctx* c, const fslr_params* p, const fslr_match_queries
   // FSLR_MATCH_BUDGET (tests): a small hit budget, so that a small batch spans several chunks
   if (const char* e = std::getenv("FSLR_MATCH_BUDGET")) budget = std::max<int64_t>(1, std::atoll(e));
   hipStream_t st = c->stream;
-  const int nt = (ni + kTile - 1) / kTile;
   MatchArgs s{};
-  s.ix = IndexView{c->crange, c->s_start, c->endkey, c->pmaxkey + nt, c->pmaxkey + 2 * static_cast<size_t>(nt), c->idx4,
-                   c->rmeta, c->have_data_pos ? c->data_pos : nullptr, nt, ni, static_cast<int>(c->n), c->n_chroms};
+  s.ix = index_view(c, nullptr);                    // (no perm: virtual reads are refused)
   int* rd = w->rd;
   s.roffq = rd, s.qlen2 = rd + (kBlockReads + 1), s.nal = rd + 2 * (kBlockReads + 1), s.excl = rd + 3 * (kBlockReads + 1);
   s.qc = w->qcol, s.qs = w->qcol + kBlockIvs, s.qe = w->qcol + 2 * kBlockIvs, s.qt = w->qcol + 3 * kBlockIvs;
@@ -770,9 +652,7 @@ int fslr_match_rows(fslr_ctx* c, int32_t* partner, int32_t* I, int32_t* U, uint8
   for (int64_t k = 0; k < total; ++k) {
     const unsigned long long v = w->rows[k];
     partner[k] = static_cast<int32_t>(v & 0xffffffffull);
-    I[k] = static_cast<int32_t>((v >> 32) & 0xff);
-    U[k] = static_cast<int32_t>((v >> 40) & 0xff);
-    flags[k] = static_cast<uint8_t>(v >> 48);
+    fit_unpack(static_cast<unsigned>(v >> 32), &I[k], &U[k], &flags[k]);
   }
   return FSLR_OK;
 }

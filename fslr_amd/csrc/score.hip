@@ -28,6 +28,7 @@
 #include <string>
 
 #include "ctx.hpp"
+#include "firstfit.hpp"
 #include "fslr_hip.h"
 #include "kernels.hpp"
 #include "wave.hpp"
@@ -63,7 +64,6 @@ void fslr_score_free(fslr_ctx* c) {
 namespace {
 
 constexpr int64_t kChunk = int64_t(1) << 21;   // pairs per launch: 24 MiB of scratch at most
-constexpr int kPassBytes = FSLR_MAX_L * kPassStride;
 
 struct ScoreArgs {
   const int4* rmeta;
@@ -92,9 +92,7 @@ __device__ __forceinline__ PairMeta pair_meta(const ScoreArgs& s, int k, bool va
     m.LA = ma.y & 0xffff;
     m.offB = mb.x;
     m.LB = mb.y & 0xffff;
-    bool zd = false;
-    const bool pass = lengths_pass(ma.z, mb.z, ma.w, mb.w, s.qcut, s.ncut, &zd);
-    m.gate = zd ? FSLR_SCORE_ZD_GATE : pass ? FSLR_SCORE_GATE : 0;
+    m.gate = gate_flags(ma.z, mb.z, ma.w, mb.w, s.qcut, s.ncut);
   }
   return m;
 }
@@ -115,8 +113,7 @@ __device__ __forceinline__ void score_groups(const ScoreArgs& s, int k, bool val
   max_la = max(max_la, __shfl_xor(max_la, 16));
   max_la = max(max_la, __shfl_xor(max_la, 32));
   max_la = rdl(max_la, 0);
-  bool used = false, zd = false;
-  int I = 0;
+  FirstFit ff;
   for (int r0 = 0; r0 < max_la; r0 += W) {
     int4 ai = make_int4(-1, 0, 0, 0);
     if (valid && r0 + l < m.LA) {
@@ -132,38 +129,10 @@ __device__ __forceinline__ void score_groups(const ScoreArgs& s, int k, bool val
         const int src = gbase | i;
         c = __shfl(ai.x, src), si = __shfl(ai.y, src), ei = __shfl(ai.z, src), ti = __shfl(ai.w, src);
       }
-      const bool cand = col && !zd && r0 + i < m.LA && !used && bj.x == c;
-      // FSLR_THR_ZERO_ALN is a sentinel thr_ok would accept: tested before iv_match_general
-      const bool zero = cand && (ti == FSLR_THR_ZERO_ALN || bj.w == FSLR_THR_ZERO_ALN);
-      const bool hit = cand && (zero || iv_match_general(si, ei, ti, bj.y, bj.z, bj.w));
-      unsigned long long hm = __ballot(hit), zm = __ballot(zero);
-      if constexpr (W < kWave) {
-        hm = (hm >> gbase) & ((1ull << W) - 1);
-        zm >>= gbase;
-      }
-      if (hm) {
-        const int j = __builtin_ctzll(hm);
-        if ((zm >> j) & 1ull) {
-          zd = true;                 // the row's walk meets the aln_size == 0 column before any match
-        } else {
-          used |= l == j;
-          ++I;
-        }
-      }
+      ff.row<W>(c, si, ei, ti, r0 + i < m.LA, bj, col, lane);
     }
   }
-  if (valid && l == 0) {
-    int U = m.LA + m.LB - I, flags = m.gate;
-    if (zd) {
-      I = U = 0;
-      flags |= FSLR_SCORE_ZD_OVERLAP;
-    } else if ((flags & FSLR_SCORE_GATE) && I > 0) {
-      const int t = (I - 1) * kPassStride + (U - 1);
-      FSLR_BOUND(t, kPassBytes);
-      if (s.pt[t]) flags |= FSLR_SCORE_EDGE;
-    }
-    s.out[k] = static_cast<unsigned>(I) | (static_cast<unsigned>(U) << 8) | (static_cast<unsigned>(flags) << 16);
-  }
+  if (valid && l == 0) s.out[k] = fit_result(m.LA, m.LB, ff.I, ff.zd, m.gate, s.pt);
 }
 
 __global__ __launch_bounds__(256) void k_score_pairs(ScoreArgs s) {
@@ -264,12 +233,7 @@ int fslr_score_pairs(fslr_ctx* c, const fslr_params* p, int64_t n_pairs, const i
     HIP_TRY(c, hipMemcpyAsync(w->host, w->out, mb, hipMemcpyDeviceToHost, st));
     if (prof) HIP_TRY(c, hipEventRecord(w->ev[3], st));
     HIP_TRY(c, hipStreamSynchronize(st));
-    for (int64_t k = 0; k < m; ++k) {
-      const unsigned v = w->host[k];
-      I[k0 + k] = static_cast<int32_t>(v & 0xff);
-      U[k0 + k] = static_cast<int32_t>((v >> 8) & 0xff);
-      flags[k0 + k] = static_cast<uint8_t>(v >> 16);
-    }
+    for (int64_t k = 0; k < m; ++k) fit_unpack(w->host[k], &I[k0 + k], &U[k0 + k], &flags[k0 + k]);
     if (prof)
       for (int t = 0; t < 3; ++t) {
         float ms = 0;

@@ -9,7 +9,8 @@
 // iv_data_pos[k] where the reads came with it, else the CSR index k.
 //
 // Passes (the index parts are those of index.hip; the tile prefix and the (chrom, end) keys come from
-// ensure_bwd_ranges on the first search of an index generation, never from fslr_build_index):
+// ensure_bwd_ranges on the first search of an index generation, never from fslr_build_index; a query's
+// span, the hit test and the re-rank of equal starts are IndexView's, idxsearch.hpp, as match.hip's are):
 //   span    one lane per query: hi = upper bound of qe in the chromosome's starts; lo = the first
 //           position of the chromosome whose end reaches qs: the first 256-position tile whose
 //           prefix max of (chrom, end) reaches (c, qs) (binary search), then the first such end in
@@ -34,6 +35,7 @@
 
 #include "ctx.hpp"
 #include "fslr_hip.h"
+#include "idxsearch.hpp"
 #include "kernels.hpp"
 #include "wave.hpp"
 
@@ -85,68 +87,20 @@ void fslr_search_free(fslr_ctx* c) {
 
 namespace {
 
-constexpr int kTile = 256;             // index.hip: pmax tiles
-constexpr int kGroup = 1024;           // index.hip: tiles per scan group
 constexpr int kPiece = 64;             // span positions per piece (one wavefront)
 
-// index.hip's tile prefix: pmaxkey = tile maxima [0, nt), local group prefixes [nt, 2 nt), exclusive
-// group prefixes [2 nt, 2 nt + ng); the inclusive prefix of tile t
-struct TilePrefix {
-  const unsigned long long* loc;
-  const unsigned long long* group_excl;
-  int nt;
-  __device__ __forceinline__ unsigned long long incl(int t) const {
-    FSLR_BOUND(t, nt);
-    const unsigned long long a = group_excl[t / kGroup], b = loc[t];
-    return a > b ? a : b;
-  }
-};
-
 __global__ __launch_bounds__(256) void k_search_span(const int* __restrict__ qc, const int* __restrict__ qs_,
-                                                     const int* __restrict__ qe_, long long nq, int n_chroms,
-                                                     const int2* __restrict__ crange, const int* __restrict__ s_start,
-                                                     const unsigned long long* __restrict__ endkey, TilePrefix tp,
-                                                     int ni, int2* __restrict__ span, long long* __restrict__ npc) {
+                                                     const int* __restrict__ qe_, long long nq, IndexView ix,
+                                                     int2* __restrict__ span, long long* __restrict__ npc) {
   for (long long i = blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x; i <= nq;
        i += static_cast<long long>(gridDim.x) * blockDim.x) {
     if (i == nq) {
       npc[nq] = 0;
       break;
     }
-    const int c = qc[i], qe = qe_[i];
-    const int qs = max(qs_[i], 0);               // stored ends are >= 0: the same hits
-    int lo = 0, hi = 0;
-    if (c >= 0 && c < n_chroms) {
-      const int2 cr = crange[c];
-      int a = cr.x, z = cr.y;                      // first position of the chromosome with start > qe
-      while (a < z) {
-        const int mid = (a + z) >> 1;
-        FSLR_BOUND(mid, ni);
-        if (s_start[mid] <= qe) a = mid + 1; else z = mid;
-      }
-      lo = hi = a;
-      if (hi > cr.x) {
-        // positions before cr.x hold smaller chromosomes, so their keys stay below (c, qs): the first
-        // tile from the chromosome's whose inclusive prefix reaches the key holds the first such end
-        const unsigned long long key = (static_cast<unsigned long long>(c) << 32) | static_cast<unsigned>(qs);
-        int tb = cr.x / kTile, te = (hi - 1) / kTile;
-        if (tp.incl(te) >= key) {
-          while (tb < te) {
-            const int mid = (tb + te) >> 1;
-            if (tp.incl(mid) >= key) te = mid; else tb = mid + 1;
-          }
-          int p = max(tb * kTile, cr.x);
-          const int pe = min((tb + 1) * kTile, hi);
-          for (; p < pe; ++p) {
-            FSLR_BOUND(p, ni);
-            if (static_cast<int>(static_cast<unsigned>(endkey[p])) >= qs) break;
-          }
-          lo = p;
-        }
-      }
-    }
-    span[i] = make_int2(lo, hi);
-    npc[i] = (static_cast<long long>(hi) - lo + kPiece - 1) / kPiece;
+    const int2 sp = ix.span_of(qc[i], max(qs_[i], 0), qe_[i]);   // stored ends are >= 0: the same hits
+    span[i] = sp;
+    npc[i] = (static_cast<long long>(sp.y) - sp.x + kPiece - 1) / kPiece;
   }
 }
 
@@ -166,8 +120,8 @@ __global__ __launch_bounds__(256) void k_search_heads(const long long* __restric
 
 __global__ __launch_bounds__(256) void k_search_count(const int* __restrict__ pq, const long long* __restrict__ poff,
                                                       const int2* __restrict__ span, const int* __restrict__ qs_,
-                                                      const unsigned long long* __restrict__ endkey, long long np,
-                                                      long long nq, int ni, long long* __restrict__ pcnt) {
+                                                      IndexView ix, long long np, long long nq,
+                                                      long long* __restrict__ pcnt) {
   const int lane = threadIdx.x & 63;
   const long long nw = static_cast<long long>(gridDim.x) * (blockDim.x >> 6);
   for (long long g = blockIdx.x * static_cast<long long>(blockDim.x >> 6) + (threadIdx.x >> 6); g <= np; g += nw) {
@@ -180,11 +134,7 @@ __global__ __launch_bounds__(256) void k_search_count(const int* __restrict__ pq
     const int2 sp = span[i];
     const int qs = max(qs_[i], 0);
     const long long p = sp.x + (g - poff[i]) * kPiece + lane;
-    bool hit = false;
-    if (p < sp.y) {
-      FSLR_BOUND(p, ni);
-      hit = static_cast<int>(static_cast<unsigned>(endkey[p])) >= qs;
-    }
+    const bool hit = p < sp.y && ix.reaches(p, qs);
     const unsigned long long hm = __ballot(hit);
     if (lane == 0) pcnt[g] = __popcll(hm);
   }
@@ -200,26 +150,10 @@ __global__ __launch_bounds__(256) void k_search_offsets(const long long* __restr
   }
 }
 
-struct IdMap {
-  const int4* rmeta;
-  const int* data_pos;                 // null: the data position is the uploaded CSR index
-  const int* perm;                     // null, or virtual -> real interval (fslr_set_reads_any)
-  int n, ni;
-  // the uploaded CSR's index of the interval with tag read << 6 | j, and its data position
-  __device__ __forceinline__ int2 of(int tag) const {
-    FSLR_BOUND(tag >> 6, n);
-    const int kv = rmeta[tag >> 6].x + (tag & 63);
-    FSLR_BOUND(kv, ni);
-    const int k = perm ? perm[kv] : kv;
-    return make_int2(k, data_pos ? data_pos[kv] : k);
-  }
-};
-
 __global__ __launch_bounds__(256) void k_search_fill(const int* __restrict__ pq, const long long* __restrict__ poff,
                                                      const long long* __restrict__ pscan,
                                                      const int2* __restrict__ span, const int* __restrict__ qs_,
-                                                     const int4* __restrict__ idx4, const int* __restrict__ s_start,
-                                                     IdMap ids, long long np, long long nq, long long total,
+                                                     IndexView ix, long long np, long long nq, long long total,
                                                      int* __restrict__ out) {
   const int lane = threadIdx.x & 63;
   const long long nw = static_cast<long long>(gridDim.x) * (blockDim.x >> 6);
@@ -233,8 +167,8 @@ __global__ __launch_bounds__(256) void k_search_fill(const int* __restrict__ pq,
     bool hit = false;
     int4 rec = make_int4(0, 0, 0, 0);
     if (p64 < sp.y) {
-      FSLR_BOUND(p64, ids.ni);
-      rec = idx4[p64];
+      FSLR_BOUND(p64, ix.ni);
+      rec = ix.idx4[p64];
       hit = rec.y >= qs;
     }
     const unsigned long long hm = __ballot(hit);
@@ -242,40 +176,21 @@ __global__ __launch_bounds__(256) void k_search_fill(const int* __restrict__ pq,
     const int p = static_cast<int>(p64);
     const long long base = pscan[g0], cnt = pscan[g1] - base;
     long long r = pscan[g] - base + mbcnt(hm);   // ascending rank among the query's hits, ties in index order
-    const int2 me = ids.of(rec.w);
-    const bool tied = (p > sp.x && s_start[p - 1] == rec.x) || (p + 1 < sp.y && s_start[p + 1] == rec.x);
-    if (tied) {
-      // the run of equal start inside the span: the hits of it before p leave the rank, those that
-      // precede p in (end descending, data position ascending) enter it
-      int rb = p;
-      while (rb > sp.x && s_start[rb - 1] == rec.x) --rb;
-      int before = 0, first = 0;
-      for (int f = rb; f < sp.y; ++f) {
-        FSLR_BOUND(f, ids.ni);
-        const int4 rf = idx4[f];
-        if (rf.x != rec.x) break;
-        if (rf.y < qs || f == p) continue;
-        before += f < p;
-        first += rf.y > rec.y || (rf.y == rec.y && ids.of(rf.w).y < me.y);
-      }
-      r += first - before;
-    }
+    const int2 me = ix.ids<true>(rec.w);
+    if (ix.tied(sp, p, rec.x)) r += ix.tie_shift<true>(sp, p, rec, qs, me.y);
     const long long dst = base + cnt - 1 - r;      // top-down
     FSLR_BOUND(dst, total);
     out[dst] = me.x;
   }
 }
 
-template <typename T>
-int grow(fslr_ctx* c, T** p, size_t count) { return dalloc(c, p, count); }
-
 int ensure_queries(fslr_ctx* c, SearchWork* w, int64_t nq) {
   if (w->off && nq <= w->q_cap) return FSLR_OK;
   w->q_cap = 0;
   const int64_t cap = std::max<int64_t>(nq + nq / 4, 1024);
   int rc;
-  if ((rc = grow(c, &w->q3, 3 * cap)) || (rc = grow(c, &w->span, cap)) || (rc = grow(c, &w->npc, cap + 1)) ||
-      (rc = grow(c, &w->poff, cap + 1)) || (rc = grow(c, &w->off, cap + 1)))
+  if ((rc = dalloc(c, &w->q3, 3 * cap)) || (rc = dalloc(c, &w->span, cap)) || (rc = dalloc(c, &w->npc, cap + 1)) ||
+      (rc = dalloc(c, &w->poff, cap + 1)) || (rc = dalloc(c, &w->off, cap + 1)))
     return rc;
   w->q_cap = cap;
   return FSLR_OK;
@@ -303,21 +218,9 @@ int ensure_pieces(fslr_ctx* c, SearchWork* w, int64_t np) {
   w->p_cap = 0;                                   // (a failed growth leaves no buffer behind its capacity)
   const int64_t cap = std::max<int64_t>(np + np / 4, 4096);
   int rc;
-  if ((rc = grow(c, &w->pqh, cap)) || (rc = grow(c, &w->pq, cap)) || (rc = grow(c, &w->pcnt, cap + 1)) || (rc = grow(c, &w->pscan, cap + 1)))
+  if ((rc = dalloc(c, &w->pqh, cap)) || (rc = dalloc(c, &w->pq, cap)) || (rc = dalloc(c, &w->pcnt, cap + 1)) || (rc = dalloc(c, &w->pscan, cap + 1)))
     return rc;
   w->p_cap = cap;
-  return FSLR_OK;
-}
-
-int wave_grid(long long waves) { return grid_for(waves, 4, 256 * 32); }
-
-// why this context cannot answer a search, or FSLR_OK
-int search_state(fslr_ctx* c) {
-  if (!c->index_built) return fail(c, FSLR_ERR_STATE, "fslr_search: fslr_build_index first");
-  if (c->filter_active)
-    return fail(c, FSLR_ERR_STATE, "fslr_search: a chromosome or position filter is active (the index is partial)");
-  if (c->n_shards > 1 || c->built_n_shards > 1)
-    return fail(c, FSLR_ERR_STATE, "fslr_search: the index was built for one of several shards (it is partial)");
   return FSLR_OK;
 }
 
@@ -330,7 +233,7 @@ int fslr_search(fslr_ctx* c, int64_t nq, const int32_t* chrom, const int32_t* st
   if (!c) return FSLR_ERR_INVALID;
   if (nq < 0 || nq >= (int64_t(1) << 31) - 1) return fail(c, FSLR_ERR_INVALID, "fslr_search: query count out of range");
   if (nq && (!chrom || !start || !end)) return fail(c, FSLR_ERR_INVALID, "fslr_search: null query array");
-  if (int rc = search_state(c)) return rc;
+  if (int rc = search_state(c, "fslr_search")) return rc;
   HIP_TRY(c, hipSetDevice(c->device));
   if (!c->srw) c->srw = new SearchWork();
   SearchWork* w = c->srw;
@@ -365,11 +268,9 @@ int fslr_search(fslr_ctx* c, int64_t nq, const int32_t* chrom, const int32_t* st
   HIP_TRY(c, hipMemcpyAsync(qc, chrom, qb, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(qs, start, qb, hipMemcpyHostToDevice, st));
   HIP_TRY(c, hipMemcpyAsync(qe, end, qb, hipMemcpyHostToDevice, st));
-  const int nt = (ni + kTile - 1) / kTile;
-  const TilePrefix tp{c->pmaxkey + nt, c->pmaxkey + 2 * static_cast<size_t>(nt), nt};
+  const IndexView ix = index_view(c, nullptr);
   if (prof) HIP_TRY(c, hipEventRecord(w->ev[0], st));
-  k_search_span<<<grid_for(nq + 1), 256, 0, st>>>(qc, qs, qe, nq, c->n_chroms, c->crange, c->s_start, c->endkey, tp, ni,
-                                                  w->span, w->npc);
+  k_search_span<<<grid_for(nq + 1), 256, 0, st>>>(qc, qs, qe, nq, ix, w->span, w->npc);
   HIP_TRY(c, hipGetLastError());
   if (prof) HIP_TRY(c, hipEventRecord(w->ev[1], st));
   size_t tb = w->temp_bytes;
@@ -391,7 +292,7 @@ int fslr_search(fslr_ctx* c, int64_t nq, const int32_t* chrom, const int32_t* st
   tb = w->temp_bytes;
   HIP_TRY(c, hipcub::DeviceScan::InclusiveScan(w->temp, tb, w->pqh, w->pq, hipcub::Max(), np, st));
   if (prof) HIP_TRY(c, hipEventRecord(w->ev[2], st));
-  k_search_count<<<wave_grid(np + 1), 256, 0, st>>>(w->pq, w->poff, w->span, qs, c->endkey, np, nq, ni, w->pcnt);
+  k_search_count<<<wave_grid(np + 1), 256, 0, st>>>(w->pq, w->poff, w->span, qs, ix, np, nq, w->pcnt);
   HIP_TRY(c, hipGetLastError());
   if (prof) HIP_TRY(c, hipEventRecord(w->ev[3], st));
   tb = w->temp_bytes;
@@ -419,7 +320,7 @@ int fslr_search_hits(fslr_ctx* c, int32_t* hits, int64_t capacity) {
   SearchWork* w = c->srw;
   if (!w || !w->valid || w->reads_gen != c->reads_gen || w->index_gen != c->index_gen)
     return fail(c, FSLR_ERR_STATE, "fslr_search_hits: fslr_search first (on these reads and this index build)");
-  if (int rc = search_state(c)) return rc;
+  if (int rc = search_state(c, "fslr_search")) return rc;
   if (capacity < w->total)
     return fail(c, FSLR_ERR_INVALID, "fslr_search_hits: capacity " + std::to_string(capacity) + " < " +
                                          std::to_string(w->total) + " hits");
@@ -429,7 +330,7 @@ int fslr_search_hits(fslr_ctx* c, int32_t* hits, int64_t capacity) {
   hipStream_t st = c->stream;
   if (w->total > w->h_cap) {
     const int64_t cap = w->total + w->total / 4;
-    if (int rc = grow(c, &w->hits, cap)) {
+    if (int rc = dalloc(c, &w->hits, cap)) {
       w->h_cap = 0;
       return rc;
     }
@@ -438,7 +339,7 @@ int fslr_search_hits(fslr_ctx* c, int32_t* hits, int64_t capacity) {
   if (!c->lg_perm.empty() && w->perm_gen != c->reads_gen) {
     const int64_t m = static_cast<int64_t>(c->lg_perm.size());
     if (m > w->perm_cap) {
-      if (int rc = grow(c, &w->perm, m)) {
+      if (int rc = dalloc(c, &w->perm, m)) {
         w->perm_cap = 0;
         return rc;
       }
@@ -447,12 +348,11 @@ int fslr_search_hits(fslr_ctx* c, int32_t* hits, int64_t capacity) {
     HIP_TRY(c, hipMemcpyAsync(w->perm, c->lg_perm.data(), m * sizeof(int), hipMemcpyHostToDevice, st));
     w->perm_gen = c->reads_gen;
   }
-  const IdMap ids{c->rmeta, c->have_data_pos ? c->data_pos : nullptr, c->lg_perm.empty() ? nullptr : w->perm,
-                  static_cast<int>(c->n), static_cast<int>(c->ni)};
+  const IndexView ix = index_view(c, c->lg_perm.empty() ? nullptr : w->perm);
   const bool prof = w->ev_rec && c->prof_phases;
   if (prof) HIP_TRY(c, hipEventRecord(w->ev[5], st));
-  k_search_fill<<<wave_grid(w->np), 256, 0, st>>>(w->pq, w->poff, w->pscan, w->span, w->q3 + w->q_cap, c->idx4,
-                                                  c->s_start, ids, w->np, w->nq, w->total, w->hits);
+  k_search_fill<<<wave_grid(w->np), 256, 0, st>>>(w->pq, w->poff, w->pscan, w->span, w->q3 + w->q_cap, ix, w->np,
+                                                  w->nq, w->total, w->hits);
   HIP_TRY(c, hipGetLastError());
   if (prof) HIP_TRY(c, hipEventRecord(w->ev[6], st));
   HIP_TRY(c, hipMemcpyAsync(hits, w->hits, static_cast<size_t>(w->total) * sizeof(int), hipMemcpyDeviceToHost, st));
