@@ -48,7 +48,8 @@ EXPORTED = ['fslr_abi_version', 'fslr_last_error', 'fslr_ctx_create', 'fslr_ctx_
             'fslr_coverage_build', 'fslr_coverage_at', 'fslr_coverage_timings',
             'fslr_cluster_table', 'fslr_get_cluster_ids', 'fslr_get_cluster_members', 'fslr_assign_clusters',
             'fslr_choose_representatives', 'fslr_cluster_timings',
-            'fslr_match_reads', 'fslr_match_rows', 'fslr_match_timings']
+            'fslr_match_reads', 'fslr_match_rows', 'fslr_match_timings', 'fslr_score_pairs_any',
+            'fslr_match_reads_any', 'fslr_match_rows_any']
 # fslr_score_pairs' flag bits (include/fslr_hip.h)
 SCORE_GATE, SCORE_EDGE, SCORE_ZD_GATE, SCORE_ZD_OVERLAP = 1, 2, 4, 8
 # fslr_coverage_*: keys per tile of the sorted arrays, queries per chunk (include/fslr_hip.h)
@@ -234,9 +235,13 @@ def load(path: str = LIB_PATH):
         'fslr_search_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         'fslr_score_pairs': (ctypes.c_int, [vp, ctypes.POINTER(Params), i64, vp, vp, vp, vp, vp]),
         'fslr_score_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        'fslr_score_pairs_any': (ctypes.c_int, [vp, ctypes.POINTER(Params), vp, i32, i64, vp, vp, vp, vp, vp]),
         'fslr_match_reads': (ctypes.c_int, [vp, ctypes.POINTER(Params), ctypes.POINTER(MatchQueries), ctypes.c_uint32,
                                             vp, vp, vp, ctypes.POINTER(ctypes.c_int64)]),
         'fslr_match_rows': (ctypes.c_int, [vp, vp, vp, vp, vp, i64]),
+        'fslr_match_reads_any': (ctypes.c_int, [vp, ctypes.POINTER(Params), vp, i32, ctypes.POINTER(MatchQueries),
+                                                ctypes.c_uint32, vp, vp, vp, ctypes.POINTER(ctypes.c_int64)]),
+        'fslr_match_rows_any': (ctypes.c_int, [vp, vp, vp, vp, vp, i64]),
         'fslr_match_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         'fslr_coverage_build': (ctypes.c_int, [vp, i64, i32, vp, vp, vp]),
         'fslr_coverage_at': (ctypes.c_int, [vp, i64, vp, vp, vp]),
@@ -907,6 +912,26 @@ class Context:
                                              _ptr(flags)))
         return I, U, flags
 
+    def score_pairs_any(self, a, b, qlen_cut, nal_cut, pass_table, umax=None):
+        """score_pairs for reads of any length (fslr_score_pairs_any): ``a`` and ``b`` are real read ranks (the
+        reads as load_csr_any numbered them), a read's list is its whole real list, I and U are unclamped.
+        ``umax`` (prep.umax_table over the longest read) decides EDGE beyond the pass table; it is required
+        when the context holds reads of more than FSLR_MAX_L intervals."""
+        a, b = (np.ascontiguousarray(x, dtype=np.int32) for x in (a, b))
+        if not (a.ndim == 1 and a.shape == b.shape):
+            raise ValueError('a and b must be one-dimensional and of one length')
+        um = None
+        if umax is not None:
+            um = np.ascontiguousarray(umax, dtype=np.int32)
+            if um.ndim != 1:
+                raise ValueError('umax must be one-dimensional')
+        p = self._params(qlen_cut, nal_cut, pass_table, 0)
+        I, U, flags = np.zeros(a.size, np.int32), np.zeros(a.size, np.int32), np.zeros(a.size, np.uint8)
+        self._check(self._L.fslr_score_pairs_any(self._h, ctypes.byref(p), _ptr(um) if um is not None else None,
+                                                 int(um.size) if um is not None else 0, int(a.size), _ptr(a), _ptr(b),
+                                                 _ptr(I), _ptr(U), _ptr(flags)))
+        return I, U, flags
+
     def score_timings(self) -> dict:
         """HIP-event times (ms) of the last score_pairs (profiling contexts), summed over its chunks."""
         ms = (ctypes.c_float * 3)()
@@ -916,6 +941,28 @@ class Context:
     # -- new reads against the resident index (fslr_hip.h fslr_match_reads / fslr_match_rows) --------
     def match_reads(self, read_off, read_qlen2, read_nal, iv_chrom, iv_start, iv_end, iv_thr, qlen_cut, nal_cut,
                     pass_table, emit_mask=SCORE_EDGE, exclude=None):
+        """The pair loop for query reads outside the uploaded set (fslr_match_reads; reads of at most FSLR_MAX_L
+        intervals on both sides): see ``_match_reads``.  The rows are fetched with ``match_rows``."""
+        return self._match_reads(False, None, read_off, read_qlen2, read_nal, iv_chrom, iv_start, iv_end, iv_thr,
+                                 qlen_cut, nal_cut, pass_table, emit_mask, exclude)
+
+    def match_reads_any(self, read_off, read_qlen2, read_nal, iv_chrom, iv_start, iv_end, iv_thr, qlen_cut, nal_cut,
+                        pass_table, emit_mask=SCORE_EDGE, exclude=None, umax=None):
+        """match_reads for reads of any length (fslr_match_reads_any): query and resident reads of up to 4096
+        intervals, ``exclude`` and the partners are real read ranks, I and U are unclamped.  ``umax``
+        (prep.umax_table over the longest list) decides EDGE beyond the pass table; it is required when the
+        context holds reads of more than FSLR_MAX_L intervals or a query read has more.  The rows are fetched
+        with ``match_rows_any``."""
+        um = None
+        if umax is not None:
+            um = np.ascontiguousarray(umax, dtype=np.int32)
+            if um.ndim != 1:
+                raise ValueError('umax must be one-dimensional')
+        return self._match_reads(True, um, read_off, read_qlen2, read_nal, iv_chrom, iv_start, iv_end, iv_thr,
+                                 qlen_cut, nal_cut, pass_table, emit_mask, exclude)
+
+    def _match_reads(self, any_length, um, read_off, read_qlen2, read_nal, iv_chrom, iv_start, iv_end, iv_thr,
+                     qlen_cut, nal_cut, pass_table, emit_mask, exclude):
         """The pair loop for query reads outside the uploaded set (a CSR like set_reads', dense chromosome
         ids, folded thresholds): ``(offsets int64[n + 1], counts int32[n, 3], best int32[n])``, counts =
         candidates, gated, edges per query read, best = the partner of the largest I / U or -1.  The rows
@@ -939,10 +986,24 @@ class Context:
         p = self._params(qlen_cut, nal_cut, pass_table, 0)
         offsets, counts, best = np.zeros(n + 1, np.int64), np.zeros((n, 3), np.int32), np.full(n, -1, np.int32)
         total = ctypes.c_int64(0)
-        self._check(self._L.fslr_match_reads(self._h, ctypes.byref(p), ctypes.byref(q), int(emit_mask), _ptr(offsets),
-                                             _ptr(counts), _ptr(best), ctypes.byref(total)))
+        if any_length:
+            self._check(self._L.fslr_match_reads_any(self._h, ctypes.byref(p), _ptr(um) if um is not None else None,
+                                                     int(um.size) if um is not None else 0, ctypes.byref(q),
+                                                     int(emit_mask), _ptr(offsets), _ptr(counts), _ptr(best),
+                                                     ctypes.byref(total)))
+        else:
+            self._check(self._L.fslr_match_reads(self._h, ctypes.byref(p), ctypes.byref(q), int(emit_mask),
+                                                 _ptr(offsets), _ptr(counts), _ptr(best), ctypes.byref(total)))
         self._match_rows = int(total.value)
         return offsets, counts, best
+
+    def match_rows_any(self):
+        """The last match_reads_any's rows, as match_rows gives match_reads'."""
+        n = getattr(self, '_match_rows', 0)
+        partner, I, U = (np.zeros(n, np.int32) for _ in range(3))
+        flags = np.zeros(n, np.uint8)
+        self._check(self._L.fslr_match_rows_any(self._h, _ptr(partner), _ptr(I), _ptr(U), _ptr(flags), n))
+        return partner, I, U, flags
 
     def match_rows(self):
         """The last match_reads' rows: ``(partner int32, I int32, U int32, flags uint8)``, query read after

@@ -622,6 +622,22 @@ class DeviceIntervalIndex:
         if self.long is not None:
             raise NotImplementedError(f'score_pairs does not take an index with reads of more than {FSLR_MAX_L} '
                                       f'intervals')
+        return self._score_pairs(query1, query2, overlap_cutoff, jaccard_threshold, qlen_diff, diff,
+                                 raise_zero_division, False)
+
+    def score_pairs_any(self, query1, query2, overlap_cutoff, jaccard_threshold, qlen_diff, diff,
+                        raise_zero_division=False) -> PairScores:
+        """score_pairs on any index, with or without reads of more than FSLR_MAX_L intervals (up to 4096, the
+        index's limit): the ranks are the reads' own, a read's list is its whole list, I and U are unclamped
+        and the edge rule beyond the pass table is ``umax_table(jaccard_threshold, longest read)``
+        (fslr_score_pairs_any).  On an index without such reads it is score_pairs, byte for byte."""
+        if not len(jaccard_threshold):
+            raise ValueError('jaccard_threshold is empty (cluster.py:188 takes its min())')
+        return self._score_pairs(query1, query2, overlap_cutoff, jaccard_threshold, qlen_diff, diff,
+                                 raise_zero_division, True)
+
+    def _score_pairs(self, query1, query2, overlap_cutoff, jaccard_threshold, qlen_diff, diff, raise_zero_division,
+                     any_length):
         a, b = self._ranks(query1), self._ranks(query2)
         if a.shape != b.shape:
             raise ValueError('query1 and query2 must be of one length')
@@ -633,7 +649,11 @@ class DeviceIntervalIndex:
         elif self.__dict__.get('_thr_key') != (float(overlap_cutoff), getattr(ctx, 'thr_gen', 0)):
             ctx.set_thresholds(fold_overlap_threshold(self.csr.iv_aln, overlap_cutoff))
             self._thr_key = (float(overlap_cutoff), ctx.thr_gen)
-        I, U, flags = ctx.score_pairs(a, b, 1 - qlen_diff, 1 - diff, pass_table(jaccard_threshold))
+        if any_length:
+            umax = umax_table(jaccard_threshold, int(self.long.max())) if self.long is not None else None
+            I, U, flags = ctx.score_pairs_any(a, b, 1 - qlen_diff, 1 - diff, pass_table(jaccard_threshold), umax)
+        else:
+            I, U, flags = ctx.score_pairs(a, b, 1 - qlen_diff, 1 - diff, pass_table(jaccard_threshold))
         qn = self.data.qnames[self.csr.read_qcode]
         if raise_zero_division:
             bad = np.flatnonzero(flags & (SCORE_ZD_GATE | SCORE_ZD_OVERLAP))
@@ -663,6 +683,22 @@ class DeviceIntervalIndex:
         if self.long is not None:
             raise NotImplementedError(f'match_reads does not take an index with reads of more than {FSLR_MAX_L} '
                                       f'intervals')
+        return self._match_reads(reads, overlap_cutoff, jaccard_threshold, qlen_diff, diff, emit, exclude, False)
+
+    def match_reads_any(self, reads, overlap_cutoff, jaccard_threshold, qlen_diff, diff, emit='edges',
+                        exclude=None) -> ReadMatches:
+        """match_reads on any index and for new reads of up to 4096 intervals (fslr_match_reads_any): partners
+        and ``exclude`` are the reads' own ranks, a long resident read is one candidate however many of its
+        intervals are hit, I and U are unclamped, and the edge rule beyond the pass table is
+        ``umax_table(jaccard_threshold, longest list)``.  On an index without long reads and for new reads of
+        at most FSLR_MAX_L intervals it is match_reads, byte for byte."""
+        if not len(jaccard_threshold):
+            raise ValueError('jaccard_threshold is empty (cluster.py:188 takes its min())')
+        if emit not in self._EMIT:
+            raise ValueError(f"emit must be 'edges', 'gated' or 'all', not {emit!r}")
+        return self._match_reads(reads, overlap_cutoff, jaccard_threshold, qlen_diff, diff, emit, exclude, True)
+
+    def _match_reads(self, reads, overlap_cutoff, jaccard_threshold, qlen_diff, diff, emit, exclude, any_length):
         if isinstance(reads, CSR):
             qcsr, chrom = reads, np.asarray(reads.iv_chrom, np.int32)
             names = np.arange(qcsr.n_reads)
@@ -677,9 +713,11 @@ class DeviceIntervalIndex:
             chrom = self._dense_chroms(raw[np.asarray(qcsr.data_pos, np.int64)]) if len(reads) else \
                 np.zeros(0, np.int32)
             names = reads.qnames[qcsr.read_qcode]
-        if has_long_reads(qcsr):
-            r = int(np.argmax(np.diff(qcsr.read_off) > FSLR_MAX_L))
-            raise ValueError(f'query read {r} has more than {FSLR_MAX_L} intervals')
+        qlen = np.diff(np.asarray(qcsr.read_off, np.int64))
+        limit = 4096 if any_length else FSLR_MAX_L
+        if qlen.size and qlen.max() > limit:
+            r = int(np.argmax(qlen > limit))
+            raise ValueError(f'query read {r} has more than {limit} intervals')
         n = qcsr.n_reads
         ex = None
         if exclude is not None:
@@ -702,11 +740,21 @@ class DeviceIntervalIndex:
         elif self.__dict__.get('_thr_key') != (float(overlap_cutoff), getattr(ctx, 'thr_gen', 0)):
             ctx.set_thresholds(fold_overlap_threshold(self.csr.iv_aln, overlap_cutoff))
             self._thr_key = (float(overlap_cutoff), ctx.thr_gen)
-        off, counts, best = ctx.match_reads(qcsr.read_off, qcsr.read_qlen2, qcsr.read_nal, chrom, qcsr.iv_start,
-                                            qcsr.iv_end, fold_overlap_threshold(qcsr.iv_aln, overlap_cutoff),
-                                            1 - qlen_diff, 1 - diff, pass_table(jaccard_threshold),
-                                            self._EMIT[emit], ex)
-        partner, I, U, flags = ctx.match_rows()
+        cols = (qcsr.read_off, qcsr.read_qlen2, qcsr.read_nal, chrom, qcsr.iv_start, qcsr.iv_end,
+                fold_overlap_threshold(qcsr.iv_aln, overlap_cutoff), 1 - qlen_diff, 1 - diff,
+                pass_table(jaccard_threshold), self._EMIT[emit], ex)
+        if any_length:
+            umax = None
+            if self.long is not None or (qlen.size and qlen.max() > FSLR_MAX_L):
+                # over the longest list of either side: the table then reaches every U = L1 + L2 - I
+                resident = int(self.long.max()) if self.long is not None else \
+                    int(np.diff(np.asarray(self.csr.read_off, np.int64)).max(initial=1))
+                umax = umax_table(jaccard_threshold, max(resident, int(qlen.max(initial=1))))
+            off, counts, best = ctx.match_reads_any(*cols, umax=umax)
+            partner, I, U, flags = ctx.match_rows_any()
+        else:
+            off, counts, best = ctx.match_reads(*cols)
+            partner, I, U, flags = ctx.match_rows()
         return ReadMatches(off, partner, I, U, flags, counts, best, names, self.data.qnames[self.csr.read_qcode])
 
     def __getitem__(self, chrom):
@@ -812,6 +860,11 @@ class MultiGpuIndex:
     def score_pairs(self, *args, **kwargs):
         raise NotImplementedError('a multi-GPU index lives in the rank processes and cannot score pairs from here; '
                                   'build it with n_gpus=1 to score pairs')
+
+    score_pairs_any = score_pairs
+
+    def match_reads_any(self, *args, **kwargs):
+        return self.match_reads(*args, **kwargs)
 
     def match_reads(self, *args, **kwargs):
         raise NotImplementedError('a multi-GPU index lives in the rank processes and cannot match reads from here; '

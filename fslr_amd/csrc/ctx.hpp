@@ -189,6 +189,7 @@ struct fslr_ctx {
   std::vector<int> lg_perm;
   int64_t lg_n_real = 0, lg_n_edges = 0;
   int lg_n_umax = 0;
+  int lg_max_len = 0;                       // the longest real read (what an _any call's umax must cover)
   int* lg_vreal = nullptr;                  // [virtual reads] real read
   int* lg_vbase = nullptr;                  // [virtual reads] index of its first interval in the real read
   int* lg_rlen = nullptr;                   // [real reads] interval count

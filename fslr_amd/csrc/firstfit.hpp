@@ -11,6 +11,7 @@
 
 #include "fslr_hip.h"
 #include "kernels.hpp"
+#include "wave.hpp"
 
 namespace fslr {
 
@@ -83,5 +84,105 @@ inline void fit_unpack(unsigned v, int32_t* I, int32_t* U, uint8_t* flags) {
   *U = static_cast<int32_t>((v >> 8) & 0xff);
   *flags = static_cast<uint8_t>(v >> 16);
 }
+
+// ---- lists of up to FSLR_MAX_ANY_L intervals --------------------------------------------------------
+
+// The first-fit of two lists of 1..FSLR_MAX_ANY_L intervals on one wavefront, chunk-outer: list2 is walked
+// 64 columns at a time (column 64 c + l on lane l); per chunk the rows of list1 that no earlier chunk
+// matched are stepped in ascending order through FirstFit::row<64>, and a row that finds a free matching
+// column there takes the lowest one.  Exact: a row's choice depends on the earlier rows
+// alone; an earlier row still unmatched when the chunk starts is stepped before it inside the chunk, and a
+// row matched in an earlier chunk never looks at this one.  rows(i) / cols(j): record i of list1 / j of
+// list2 (chrom, start, end, thr).  The matched bits: rows [64 s, 64 s + 64) on lane s, two 32-bit words.
+template <class Rows, class Cols>
+__device__ __forceinline__ void long_fit(int LA, int LB, Rows rows, Cols cols, int lane, int* I_out, bool* zd_out) {
+  unsigned done_lo = 0, done_hi = 0;
+  int matched = 0;
+  bool zd = false;
+  const int nslice = (LA + kWave - 1) / kWave;
+  for (int c0 = 0; c0 < LB && matched < LA && !zd; c0 += kWave) {
+    const bool col = c0 + lane < LB;
+    int4 bj = make_int4(-2, 0, 0, 0);
+    if (col) bj = cols(c0 + lane);
+    FirstFit ff;                                   // this chunk's columns: used, and the matches made in it
+    for (int s = 0; s < nslice && !ff.zd; ++s) {
+      const int nr = min(kWave, LA - s * kWave);
+      const unsigned long long live = nr == kWave ? ~0ull : (1ull << nr) - 1;
+      const unsigned long long have = static_cast<unsigned>(rdl(static_cast<int>(done_lo), s)) |
+                                      (static_cast<unsigned long long>(static_cast<unsigned>(rdl(static_cast<int>(done_hi), s))) << 32);
+      unsigned long long pend = ~have & live;
+      if (!pend) continue;
+      if (__ballot(col && !ff.used) == 0) break;   // every column of the chunk is taken: no row can stop here
+      int4 ai = make_int4(-1, 0, 0, 0);
+      if (lane < nr) ai = rows(s * kWave + lane);
+      unsigned long long got = 0;
+      while (pend) {
+        const int i = __builtin_ctzll(pend);
+        pend &= pend - 1;
+        const int before = ff.I;
+        ff.row<kWave>(rdl(ai.x, i), rdl(ai.y, i), rdl(ai.z, i), rdl(ai.w, i), true, bj, col, lane);
+        if (ff.zd) break;
+        if (ff.I != before) got |= 1ull << i;
+      }
+      if (lane == s) {
+        done_lo |= static_cast<unsigned>(got);
+        done_hi |= static_cast<unsigned>(got >> 32);
+      }
+      matched += __popcll(got);
+    }
+    zd = ff.zd;
+  }
+  *I_out = matched;
+  *zd_out = zd;
+}
+
+constexpr int kAnyIBits = 13, kAnyUBits = 14;      // I <= 4096, U <= 8191, four flag bits: 31 bits
+
+// the result word of the _any calls: I | U << 13 | flags << 27.  EDGE from the pass table where it reaches
+// (I <= FSLR_MAX_L and U <= 2 FSLR_MAX_L), else U <= umax[I - 1] (prep.umax_table; umax may be null where
+// no pair can leave the table)
+__device__ __forceinline__ unsigned fit_result_any(int LA, int LB, int I, bool zd, int gate, const unsigned char* pt,
+                                                   const int* umax, int n_umax) {
+  int U = LA + LB - I, flags = gate;
+  if (zd) {
+    I = U = 0;
+    flags |= FSLR_SCORE_ZD_OVERLAP;
+  } else if ((flags & FSLR_SCORE_GATE) && I > 0) {
+    bool edge;
+    if (I <= FSLR_MAX_L && U <= kPassStride) {
+      const int t = (I - 1) * kPassStride + (U - 1);
+      FSLR_BOUND(t, kPassBytes);
+      edge = pt[t] != 0;
+    } else {
+      edge = umax && I <= n_umax && U <= umax[I - 1];
+    }
+    if (edge) flags |= FSLR_SCORE_EDGE;
+  }
+  return static_cast<unsigned>(I) | (static_cast<unsigned>(U) << kAnyIBits) |
+         (static_cast<unsigned>(flags) << (kAnyIBits + kAnyUBits));
+}
+
+__host__ __device__ inline int any_I(unsigned v) { return static_cast<int>(v & ((1u << kAnyIBits) - 1)); }
+__host__ __device__ inline int any_U(unsigned v) { return static_cast<int>((v >> kAnyIBits) & ((1u << kAnyUBits) - 1)); }
+__host__ __device__ inline int any_flags(unsigned v) { return static_cast<int>(v >> (kAnyIBits + kAnyUBits)); }
+
+// (host) the wide result word's fields
+inline void fit_unpack_any(unsigned v, int32_t* I, int32_t* U, uint8_t* flags) {
+  *I = any_I(v);
+  *U = any_U(v);
+  *flags = static_cast<uint8_t>(any_flags(v));
+}
+
+// Record j of a resident real read's list: its first FSLR_MAX_L intervals lie at `off`, the rest are
+// consecutive from `off2` (long.hip's lg_off2; unused for a read of at most FSLR_MAX_L intervals)
+struct ReadList {
+  const int4* iv;
+  int off, off2, ni;
+  __device__ __forceinline__ int4 operator()(int j) const {
+    const int k = j < FSLR_MAX_L ? off + j : off2 + (j - FSLR_MAX_L);
+    FSLR_BOUND(k, ni);
+    return iv[k];
+  }
+};
 
 }  // namespace fslr

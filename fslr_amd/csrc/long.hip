@@ -306,6 +306,7 @@ extern "C" int fslr_set_long_reads(fslr_ctx* c, int64_t n_real, const int32_t* v
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   c->lg_n_real = n_real;
   c->lg_n_umax = n_umax;
+  c->lg_max_len = maxl;
   c->lg_set = true;
   c->lg_n_edges = 0;
   return FSLR_OK;

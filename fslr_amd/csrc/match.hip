@@ -7,7 +7,8 @@
 // Out of scope (the boundaries the next request meets):
 //   - the edge cap (:223-224): a matched read's loop is not part of the resident graph's cap replay,
 //     so every candidate is evaluated, however many edges the read has formed;
-//   - query or resident reads of more than FSLR_MAX_L intervals (refused);
+//   - query or resident reads of more than FSLR_MAX_ANY_L intervals (fslr_match_reads keeps refusing more
+//     than FSLR_MAX_L; fslr_match_reads_any takes them, below);
 //   - matching through the multi-GPU split (a partial index is refused, as fslr_search refuses it);
 //   - inserting matched reads into the index.
 //
@@ -34,6 +35,14 @@
 //           (rows <= hits).
 //   compact exclusive scan of the chunk's row counts, rows copied dense, then D2H
 // Every output slot is a function of the input alone: no global atomics, the same bytes on every run.
+//
+// fslr_match_reads_any: the same driver.  Without virtual reads and without a query read
+// of more than FSLR_MAX_L intervals it launches the kernels above (<false>) and keeps the old row word.
+// Otherwise the <true> instantiations run: count takes a read's intervals 64 at a time; fill writes REAL
+// partner ranks (vreal[tag >> 6]) and ranks tied hits by the real CSR index through the lg_perm copy
+// (IndexView::ids<true>); score dedupes real ranks, so the chunks of one long read are one candidate at its
+// first hit, and a candidate with LA or LB beyond FSLR_MAX_L runs alone on the wave through long_fit
+// (firstfit.hpp), list1's rows read from the block's interval columns.  The result word is the wide one.
 // Algorithmic bytes: count 8 B per span position; fill 16 B per span position + 4 B per hit; score 4 B
 // per hit, 16 B (rmeta) + 16 B x L_P per candidate, 8 B per row (twice: staged, dense).
 #include <hipcub/hipcub.hpp>
@@ -90,7 +99,15 @@ struct MatchWork {
   // the last batch (fslr_match_rows): partner | I << 32 | U << 40 | flags << 48
   std::vector<unsigned long long> rows;
   bool valid = false;
+  bool any = false, wide = false;    // the batch came from fslr_match_reads_any; its rows hold the wide word
   uint64_t reads_gen = 0, index_gen = 0;
+  int* umax = nullptr;               // [umax_cap] the _any call's cutoff table
+  int umax_cap = 0;
+  int* perm = nullptr;               // fslr_set_reads_any: virtual -> real interval (lg_perm), per reads_gen
+  int64_t perm_cap = 0;
+  uint64_t perm_gen = 0;
+  int short_max = 0;                 // the longest resident read of a context without virtual reads, per reads_gen
+  uint64_t short_gen = 0;
   hipEvent_t ev[8] = {};
   bool ev_ok = false, timed = false;
   float ms[4] = {0, 0, 0, 0};        // upload, search, dedupe + score, download
@@ -100,7 +117,7 @@ void fslr_match_free(fslr_ctx* c) {
   MatchWork* w = c->mtw;
   if (!w) return;
   void* bufs[] = {w->rd, w->qcol, w->span, w->ivcnt, w->rhits, w->hoff, w->cnt3, w->best, w->nrows, w->roff,
-                  w->pt, w->temp, w->hits, w->stage, w->dense};
+                  w->pt, w->temp, w->hits, w->stage, w->dense, w->umax, w->perm};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (w->pin) (void)hipHostFree(w->pin);
@@ -136,38 +153,48 @@ struct MatchArgs {
   int* cnt3;
   int* best;
   long long* nrows;                      // chunk-relative
+  // <true> kernels only
+  const int* vreal;                      // null, or virtual -> real read
+  const int* rlen;                       // null, or a real read's interval count
+  const int* off2;                       // where a long read's intervals beyond FSLR_MAX_L begin
+  const int* umax;
+  int n_umax;
 };
 
 __global__ __launch_bounds__(256) void k_match_count(MatchArgs s) {
   const int lane = threadIdx.x & 63;
   const int nw = gridDim.x * (blockDim.x >> 6);
   for (int r = s.r0 + blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); r < s.r1; r += nw) {
-    const int o0 = s.roffq[r] - s.ivbase, L = s.roffq[r + 1] - s.roffq[r];
-    int2 sp = make_int2(0, 0);
-    int qs = 0;
-    if (lane < L) {
-      FSLR_BOUND(o0 + lane, s.nbi);
-      qs = max(s.qs[o0 + lane], 0);                // stored ends are >= 0: the same hits
-      sp = s.ix.span_of(s.qc[o0 + lane], qs, s.qe[o0 + lane]);
-      s.span[o0 + lane] = sp;
-    }
+    const int ob = s.roffq[r] - s.ivbase, Lr = s.roffq[r + 1] - s.roffq[r];
     long long tot = 0;
-    int mine = 0;
-    for (int i = 0; i < L; ++i) {
-      const int lo = rdl(sp.x, i), hi = rdl(sp.y, i), q = rdl(qs, i);
-      int cnt = 0;
-      for (int p0 = lo; p0 < hi; p0 += kWave) {
-        const int p = p0 + lane;
-        cnt += __popcll(__ballot(p < hi && s.ix.reaches(p, q)));
+    for (int b0 = 0; b0 < Lr; b0 += kWave) {       // 64 intervals at a time (one pass up to FSLR_MAX_L)
+      const int o0 = ob + b0, L = min(kWave, Lr - b0);
+      int2 sp = make_int2(0, 0);
+      int qs = 0;
+      if (lane < L) {
+        FSLR_BOUND(o0 + lane, s.nbi);
+        qs = max(s.qs[o0 + lane], 0);              // stored ends are >= 0: the same hits
+        sp = s.ix.span_of(s.qc[o0 + lane], qs, s.qe[o0 + lane]);
+        s.span[o0 + lane] = sp;
       }
-      if (lane == i) mine = cnt;
-      tot += cnt;
+      int mine = 0;
+      for (int i = 0; i < L; ++i) {
+        const int lo = rdl(sp.x, i), hi = rdl(sp.y, i), q = rdl(qs, i);
+        int cnt = 0;
+        for (int p0 = lo; p0 < hi; p0 += kWave) {
+          const int p = p0 + lane;
+          cnt += __popcll(__ballot(p < hi && s.ix.reaches(p, q)));
+        }
+        if (lane == i) mine = cnt;
+        tot += cnt;
+      }
+      if (lane < L) s.ivcnt[o0 + lane] = mine;
     }
-    if (lane < L) s.ivcnt[o0 + lane] = mine;
     if (lane == 0) s.rhits[r] = tot;
   }
 }
 
+template <bool kAny>
 __global__ __launch_bounds__(256) void k_match_fill(MatchArgs s) {
   const int lane = threadIdx.x & 63;
   const int nw = gridDim.x * (blockDim.x >> 6);
@@ -194,10 +221,14 @@ __global__ __launch_bounds__(256) void k_match_fill(MatchArgs s) {
         if (hit) {
           int rk = asc + mbcnt(hm);                // ascending rank among the interval's hits, ties in index order
           // (its data position is looked up for a tied hit only)
-          if (ix.tied(sp, p, rec.x)) rk += ix.tie_shift<false>(sp, p, rec, qs, ix.ids<false>(rec.w).y);
+          if (ix.tied(sp, p, rec.x))
+            rk += ix.template tie_shift<kAny>(sp, p, rec, qs, ix.template ids<kAny>(rec.w).y);
           const long long dst = base + cnt - 1 - rk;   // top-down
           FSLR_BOUND(dst, s.h_cap);
-          s.hits[dst] = static_cast<int>(static_cast<unsigned>(rec.w) >> 6);
+          int partner = static_cast<int>(static_cast<unsigned>(rec.w) >> 6);
+          if constexpr (kAny)
+            if (s.vreal) partner = s.vreal[partner];   // a chunk's hits are its real read's
+          s.hits[dst] = partner;
         }
         asc += __popcll(hm);
       }
@@ -208,7 +239,7 @@ __global__ __launch_bounds__(256) void k_match_fill(MatchArgs s) {
 
 // 64 / W candidates side by side, candidate k on the W-lane group of this lane: the first-fit of firstfit.hpp
 // with list1 = the query read's LA rows in LDS (uniform over the wave), list2's columns on the group's lanes
-template <int W>
+template <int W, bool kAny>
 __device__ __forceinline__ void match_groups(const MatchArgs& s, const int4* qiv, int LA, int k, bool valid, int offB,
                                              int LB, int gate, int lane, unsigned* res) {
   const int l = lane & (W - 1);
@@ -223,24 +254,47 @@ __device__ __forceinline__ void match_groups(const MatchArgs& s, const int4* qiv
     const int4 a = qiv[i];
     ff.row<W>(a.x, a.y, a.z, a.w, true, bj, col, lane);
   }
-  if (valid && l == 0) res[k] = fit_result(LA, LB, ff.I, ff.zd, gate, s.pt);
+  if (valid && l == 0) {
+    if constexpr (kAny)
+      res[k] = fit_result_any(LA, LB, ff.I, ff.zd, gate, s.pt, s.umax, s.n_umax);
+    else
+      res[k] = fit_result(LA, LB, ff.I, ff.zd, gate, s.pt);
+  }
 }
+
+// list1 of a long first-fit: the query read's rows from the block's interval columns
+struct QueryRows {
+  const int *qc, *qs, *qe, *qt;
+  int o0, nbi;
+  __device__ __forceinline__ int4 operator()(int i) const {
+    FSLR_BOUND(o0 + i, nbi);
+    return make_int4(qc[o0 + i], qs[o0 + i], qe[o0 + i], qt[o0 + i]);
+  }
+};
 
 struct CandMeta {
   int offB, LB, gate;
+  int offB2;                           // <true>: where a long partner's intervals beyond FSLR_MAX_L begin
   bool score;                          // false: no candidate here, or one that cannot be emitted
 };
 
 // candidate k of the batch (valid: k is one): the partner's CSR row and the length gate against Q
+template <bool kAny>
 __device__ __forceinline__ CandMeta cand_meta(const MatchArgs& s, const int* cand, int k, bool valid, int q2, int qn,
                                               unsigned* res) {
-  CandMeta m{0, 0, 0, false};
+  CandMeta m{0, 0, 0, 0, false};
   if (valid) {
     const int p = cand[k];
     FSLR_BOUND(p, s.ix.n);
     const int4 mb = s.ix.rmeta[p];
     m.offB = mb.x;
     m.LB = mb.y & 0xffff;
+    if constexpr (kAny) {
+      if (s.rlen) {
+        m.LB = s.rlen[p];
+        if (m.LB > FSLR_MAX_L) m.offB2 = s.off2[p];
+      }
+    }
     m.gate = gate_flags(q2, mb.z, qn, mb.w, s.qcut, s.ncut);
     // a candidate with the gate clear can carry ZD_GATE and ZD_OVERLAP only: where the mask asks for neither
     // that it has nor for ZD_OVERLAP, no row can come of it and its first-fit is skipped
@@ -250,7 +304,9 @@ __device__ __forceinline__ CandMeta cand_meta(const MatchArgs& s, const int* can
   return m;
 }
 
+template <bool kAny>
 __global__ __launch_bounds__(256) void k_match_score(MatchArgs s) {
+  constexpr int kFlagShift = kAny ? kAnyIBits + kAnyUBits : 16;
   __shared__ int4 sh_q[kWavesPerBlock][FSLR_MAX_L];
   __shared__ int sh_key[kWavesPerBlock][kSetSlots];
   __shared__ int sh_seq[kWavesPerBlock][kSetSlots];
@@ -268,7 +324,7 @@ __global__ __launch_bounds__(256) void k_match_score(MatchArgs s) {
     const int q2 = s.qlen2[r], qn = s.nal[r], excl = s.excl[r];
     const long long H = s.rhits[r], base = s.hoff[r];
     wave_lds_sync();                               // the previous read's LDS reads are done
-    if (lane < LA) {
+    if (lane < LA && lane < FSLR_MAX_L) {          // (a longer read's rows are read from the columns)
       FSLR_BOUND(o0 + lane, s.nbi);
       qiv[lane] = make_int4(s.qc[o0 + lane], s.qs[o0 + lane], s.qe[o0 + lane], s.qt[o0 + lane]);
     }
@@ -339,23 +395,42 @@ __global__ __launch_bounds__(256) void k_match_score(MatchArgs s) {
       for (int g0 = 0; g0 < nn; g0 += 4) {
         const int k = g0 + (lane >> 4);
         const bool v = k < nn;
-        const CandMeta m = cand_meta(s, cand, k, v, q2, qn, res);
-        if (v && !m.score && (lane & 15) == 0) res[k] = static_cast<unsigned>(m.gate) << 16;
+        const CandMeta m = cand_meta<kAny>(s, cand, k, v, q2, qn, res);
+        if (v && !m.score && (lane & 15) == 0) res[k] = static_cast<unsigned>(m.gate) << kFlagShift;
+        if constexpr (kAny) {
+          if (LA > FSLR_MAX_L || __ballot(m.score && m.LB > FSLR_MAX_L) != 0) {
+            // a list beyond one wavefront of lanes: the group's candidates one at a time
+            for (int q = 0; q < 4 && g0 + q < nn; ++q) {
+              const CandMeta m1 = cand_meta<kAny>(s, cand, g0 + q, true, q2, qn, res);
+              if (!m1.score) continue;
+              if (LA > FSLR_MAX_L || m1.LB > FSLR_MAX_L) {
+                int I = 0;
+                bool zd = false;
+                long_fit(LA, m1.LB, QueryRows{s.qc, s.qs, s.qe, s.qt, o0, s.nbi},
+                         ReadList{s.iv, m1.offB, m1.offB2, s.ix.ni}, lane, &I, &zd);
+                if (lane == 0) res[g0 + q] = fit_result_any(LA, m1.LB, I, zd, m1.gate, s.pt, s.umax, s.n_umax);
+              } else {
+                match_groups<64, kAny>(s, qiv, LA, g0 + q, true, m1.offB, m1.LB, m1.gate, lane, res);
+              }
+            }
+            continue;
+          }
+        }
         const bool w64 = __ballot(m.score && m.LB > 32) != 0;
         const bool w32 = __ballot(m.score && m.LB > 16) != 0;
         if (w64) {
           for (int q = 0; q < 4 && g0 + q < nn; ++q) {
-            const CandMeta m1 = cand_meta(s, cand, g0 + q, true, q2, qn, res);
-            if (m1.score) match_groups<64>(s, qiv, LA, g0 + q, true, m1.offB, m1.LB, m1.gate, lane, res);
+            const CandMeta m1 = cand_meta<kAny>(s, cand, g0 + q, true, q2, qn, res);
+            if (m1.score) match_groups<64, kAny>(s, qiv, LA, g0 + q, true, m1.offB, m1.LB, m1.gate, lane, res);
           }
         } else if (w32) {
           for (int q = 0; q < 4 && g0 + q < nn; q += 2) {
             const int k2 = g0 + q + (lane >> 5);
-            const CandMeta m2 = cand_meta(s, cand, k2, k2 < nn, q2, qn, res);
-            match_groups<32>(s, qiv, LA, k2, m2.score, m2.offB, m2.LB, m2.gate, lane, res);
+            const CandMeta m2 = cand_meta<kAny>(s, cand, k2, k2 < nn, q2, qn, res);
+            match_groups<32, kAny>(s, qiv, LA, k2, m2.score, m2.offB, m2.LB, m2.gate, lane, res);
           }
         } else {
-          match_groups<16>(s, qiv, LA, k, m.score, m.offB, m.LB, m.gate, lane, res);
+          match_groups<16, kAny>(s, qiv, LA, k, m.score, m.offB, m.LB, m.gate, lane, res);
         }
       }
       wave_lds_sync();
@@ -363,7 +438,9 @@ __global__ __launch_bounds__(256) void k_match_score(MatchArgs s) {
       const bool mine = lane < nn;
       const unsigned rv = mine ? res[lane] : 0u;
       const int pk = mine ? cand[lane] : 0;
-      const int fl = static_cast<int>(rv >> 16), ci = static_cast<int>(rv & 0xff), cu = static_cast<int>((rv >> 8) & 0xff);
+      const int fl = kAny ? any_flags(rv) : static_cast<int>(rv >> 16);
+      const int ci = kAny ? any_I(rv) : static_cast<int>(rv & 0xff);
+      const int cu = kAny ? any_U(rv) : static_cast<int>((rv >> 8) & 0xff);
       ncand += nn;
       ngated += __popcll(__ballot(mine && (fl & FSLR_SCORE_GATE)));
       unsigned long long em = __ballot(mine && (fl & FSLR_SCORE_EDGE));
@@ -456,41 +533,67 @@ int match_state(fslr_ctx* c, const char* who) {
   return FSLR_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int fslr_match_reads(fslr_ctx* c, const fslr_params* p, const fslr_match_queries* q, uint32_t emit_mask,
-                     int64_t* row_off, int32_t* counts, int32_t* best, int64_t* n_rows) {
+// either entry point.  any: fslr_match_reads_any (real ranks, reads of up to FSLR_MAX_ANY_L intervals, umax); the
+// <true> kernels and the wide row word only where the context holds virtual reads or a query read exceeds
+// FSLR_MAX_L intervals
+int match_run(fslr_ctx* c, bool any, const fslr_params* p, const int32_t* umax, int32_t n_umax,
+              const fslr_match_queries* q, uint32_t emit_mask, int64_t* row_off, int32_t* counts, int32_t* best,
+              int64_t* n_rows) {
   if (!c) return FSLR_ERR_INVALID;
-  if (!p || !p->pass_table) return fail(c, FSLR_ERR_INVALID, "fslr_match_reads: null params or pass_table");
-  if (!q) return fail(c, FSLR_ERR_INVALID, "fslr_match_reads: null queries");
+  const std::string who = any ? "fslr_match_reads_any" : "fslr_match_reads";
+  if (!p || !p->pass_table) return fail(c, FSLR_ERR_INVALID, who + ": null params or pass_table");
+  if (!q) return fail(c, FSLR_ERR_INVALID, who + ": null queries");
   const int64_t nr = q->n_reads;
   if (nr < 0 || q->n_intervals < 0 || q->n_intervals >= (int64_t(1) << 31) - 1)
-    return fail(c, FSLR_ERR_INVALID, "fslr_match_reads: read or interval count out of range");
+    return fail(c, FSLR_ERR_INVALID, who + ": read or interval count out of range");
   if (nr && (!q->read_off || !q->read_qlen2 || !q->read_nal))
-    return fail(c, FSLR_ERR_INVALID, "fslr_match_reads: null read array");
+    return fail(c, FSLR_ERR_INVALID, who + ": null read array");
   if (q->n_intervals && (!q->iv_chrom || !q->iv_start || !q->iv_end || !q->iv_thr))
-    return fail(c, FSLR_ERR_INVALID, "fslr_match_reads: null interval array");
-  if (int rc = match_state(c, "fslr_match_reads")) return rc;
+    return fail(c, FSLR_ERR_INVALID, who + ": null interval array");
+  if (int rc = any ? search_state(c, who.c_str()) : match_state(c, who.c_str())) return rc;
   if (nr && (q->read_off[0] < 0 || q->read_off[nr] > q->n_intervals))
-    return fail(c, FSLR_ERR_INVALID, "fslr_match_reads: read_off does not lie in [0, n_intervals]");
+    return fail(c, FSLR_ERR_INVALID, who + ": read_off does not lie in [0, n_intervals]");
+  const int64_t n_res = any && c->lg_set ? c->lg_n_real : c->n;     // the rank space of exclude and partner
+  const int64_t max_l = any ? FSLR_MAX_ANY_L : FSLR_MAX_L;
+  int64_t longest = 0;
   for (int64_t r = 0; r < nr; ++r) {
     const int64_t L = static_cast<int64_t>(q->read_off[r + 1]) - q->read_off[r];
     if (L < 0)
-      return fail(c, FSLR_ERR_INVALID, "fslr_match_reads: read_off decreases at query read " + std::to_string(r));
-    if (L > FSLR_MAX_L)
-      return fail(c, FSLR_ERR_INVALID, "fslr_match_reads: query read " + std::to_string(r) + " has " +
-                                           std::to_string(L) + " intervals (limit " + std::to_string(FSLR_MAX_L) + ")");
-    if (q->exclude && (q->exclude[r] < -1 || q->exclude[r] >= c->n))
-      return fail(c, FSLR_ERR_INVALID, "fslr_match_reads: exclude[" + std::to_string(r) + "] = " +
+      return fail(c, FSLR_ERR_INVALID, who + ": read_off decreases at query read " + std::to_string(r));
+    if (L > max_l)
+      return fail(c, FSLR_ERR_INVALID, who + ": query read " + std::to_string(r) + " has " +
+                                           std::to_string(L) + " intervals (limit " + std::to_string(max_l) + ")");
+    longest = std::max(longest, L);
+    if (q->exclude && (q->exclude[r] < -1 || q->exclude[r] >= n_res))
+      return fail(c, FSLR_ERR_INVALID, who + ": exclude[" + std::to_string(r) + "] = " +
                                            std::to_string(q->exclude[r]) + " is neither -1 nor a rank in [0, " +
-                                           std::to_string(c->n) + ")");
+                                           std::to_string(n_res) + ")");
   }
+  const bool wide = any && (c->lg_set || longest > FSLR_MAX_L);
   HIP_TRY(c, hipSetDevice(c->device));
   if (!c->mtw) c->mtw = new MatchWork();
   MatchWork* w = c->mtw;
+  if (wide) {
+    // umax must cover I up to the longest resident real read (I <= L2); checked before anything runs
+    int need = c->lg_max_len;
+    if (!c->lg_set) {
+      if (w->short_gen != c->reads_gen || !w->short_max) {
+        std::vector<unsigned char> l8(static_cast<size_t>(c->n));
+        if (c->n) HIP_TRY(c, hipMemcpy(l8.data(), c->rlen8, l8.size(), hipMemcpyDeviceToHost));
+        int m = 0;
+        for (unsigned char v : l8) m = std::max<int>(m, v);
+        w->short_max = m;
+        w->short_gen = c->reads_gen;
+      }
+      need = w->short_max;
+    }
+    if (!umax || n_umax < need)
+      return fail(c, FSLR_ERR_INVALID, who + ": reads of more than " + std::to_string(FSLR_MAX_L) +
+                                           " intervals: umax must cover I up to the longest resident read (" +
+                                           std::to_string(need) + ")");
+  }
   w->valid = w->timed = false;
+  w->any = any, w->wide = wide;
   w->rows.clear();
   for (float& m : w->ms) m = 0;
   auto done = [&]() {
@@ -519,7 +622,28 @@ int fslr_match_reads(fslr_ctx* c, const fslr_params* p, const fslr_match_queries
   if (const char* e = std::getenv("FSLR_MATCH_BUDGET")) budget = std::max<int64_t>(1, std::atoll(e));
   hipStream_t st = c->stream;
   MatchArgs s{};
-  s.ix = index_view(c, nullptr);                    // (no perm: virtual reads are refused)
+  if (wide) {
+    if (n_umax > w->umax_cap) {
+      w->umax_cap = 0;
+      if (int rc = dalloc(c, &w->umax, n_umax)) return rc;
+      w->umax_cap = n_umax;
+    }
+    HIP_TRY(c, hipMemcpyAsync(w->umax, umax, static_cast<size_t>(n_umax) * sizeof(int), hipMemcpyHostToDevice, st));
+    if (!c->lg_perm.empty() && w->perm_gen != c->reads_gen) {
+      const int64_t m = static_cast<int64_t>(c->lg_perm.size());
+      if (m > w->perm_cap) {
+        w->perm_cap = 0;
+        if (int rc = dalloc(c, &w->perm, m)) return rc;
+        w->perm_cap = m;
+      }
+      HIP_TRY(c, hipMemcpyAsync(w->perm, c->lg_perm.data(), m * sizeof(int), hipMemcpyHostToDevice, st));
+      w->perm_gen = c->reads_gen;
+    }
+    s.umax = w->umax, s.n_umax = n_umax;
+    if (c->lg_set) s.vreal = c->lg_vreal, s.rlen = c->lg_rlen, s.off2 = c->lg_off2;
+  }
+  // (the old kernels refuse virtual reads and look at no perm)
+  s.ix = index_view(c, wide && !c->lg_perm.empty() ? w->perm : nullptr);
   int* rd = w->rd;
   s.roffq = rd, s.qlen2 = rd + (kBlockReads + 1), s.nal = rd + 2 * (kBlockReads + 1), s.excl = rd + 3 * (kBlockReads + 1);
   s.qc = w->qcol, s.qs = w->qcol + kBlockIvs, s.qe = w->qcol + 2 * kBlockIvs, s.qt = w->qcol + 3 * kBlockIvs;
@@ -579,7 +703,7 @@ int fslr_match_reads(fslr_ctx* c, const fslr_params* p, const fslr_match_queries
     int64_t sum = 0, need = 1;
     for (int r = 0; r < m; ++r) {
       if (pin_hits[r] >= (int64_t(1) << 31) - kWave)
-        return fail(c, FSLR_ERR_NOMEM, "fslr_match_reads: query read " + std::to_string(b0 + r) + " has " +
+        return fail(c, FSLR_ERR_NOMEM, who + ": query read " + std::to_string(b0 + r) + " has " +
                                            std::to_string(pin_hits[r]) + " hits (limit 2^31)");
       if (r > cuts.back() && sum + pin_hits[r] > budget) {
         cuts.push_back(r);
@@ -597,12 +721,18 @@ int fslr_match_reads(fslr_ctx* c, const fslr_params* p, const fslr_match_queries
       const int r0 = cuts[k], r1 = cuts[k + 1], mc = r1 - r0;
       s.r0 = r0, s.r1 = r1;
       HIP_TRY(c, mark(1, 0));
-      k_match_fill<<<wave_grid(mc), 256, 0, st>>>(s);
+      if (wide)
+        k_match_fill<true><<<wave_grid(mc), 256, 0, st>>>(s);
+      else
+        k_match_fill<false><<<wave_grid(mc), 256, 0, st>>>(s);
       HIP_TRY(c, hipGetLastError());
       HIP_TRY(c, mark(1, 1));
       HIP_TRY(c, mark(2, 0));
       HIP_TRY(c, hipMemsetAsync(w->nrows + mc, 0, sizeof(long long), st));
-      k_match_score<<<wave_grid(mc), 256, 0, st>>>(s);
+      if (wide)
+        k_match_score<true><<<wave_grid(mc), 256, 0, st>>>(s);
+      else
+        k_match_score<false><<<wave_grid(mc), 256, 0, st>>>(s);
       HIP_TRY(c, hipGetLastError());
       size_t tb = w->temp_bytes;
       HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(w->temp, tb, w->nrows, w->roff, mc + 1, st));
@@ -637,24 +767,53 @@ int fslr_match_reads(fslr_ctx* c, const fslr_params* p, const fslr_match_queries
   return done();
 }
 
-int fslr_match_rows(fslr_ctx* c, int32_t* partner, int32_t* I, int32_t* U, uint8_t* flags, int64_t capacity) {
+// the saved batch of one entry point's kind, unpacked
+int rows_out(fslr_ctx* c, bool any, int32_t* partner, int32_t* I, int32_t* U, uint8_t* flags, int64_t capacity) {
   if (!c) return FSLR_ERR_INVALID;
+  const std::string who = any ? "fslr_match_rows_any" : "fslr_match_rows";
+  const std::string first = any ? "fslr_match_reads_any" : "fslr_match_reads";
   MatchWork* w = c->mtw;
-  if (!w || !w->valid || w->reads_gen != c->reads_gen || w->index_gen != c->index_gen)
-    return fail(c, FSLR_ERR_STATE, "fslr_match_rows: fslr_match_reads first (on these reads and this index build)");
-  if (int rc = match_state(c, "fslr_match_rows")) return rc;
+  if (!w || !w->valid || w->any != any || w->reads_gen != c->reads_gen || w->index_gen != c->index_gen)
+    return fail(c, FSLR_ERR_STATE, who + ": " + first + " first (on these reads and this index build)");
+  if (int rc = any ? search_state(c, who.c_str()) : match_state(c, who.c_str())) return rc;
   const int64_t total = static_cast<int64_t>(w->rows.size());
   if (capacity < total)
-    return fail(c, FSLR_ERR_INVALID, "fslr_match_rows: capacity " + std::to_string(capacity) + " < " +
+    return fail(c, FSLR_ERR_INVALID, who + ": capacity " + std::to_string(capacity) + " < " +
                                          std::to_string(total) + " rows");
   if (total == 0) return FSLR_OK;
-  if (!partner || !I || !U || !flags) return fail(c, FSLR_ERR_INVALID, "fslr_match_rows: null array");
+  if (!partner || !I || !U || !flags) return fail(c, FSLR_ERR_INVALID, who + ": null array");
   for (int64_t k = 0; k < total; ++k) {
     const unsigned long long v = w->rows[k];
     partner[k] = static_cast<int32_t>(v & 0xffffffffull);
-    fit_unpack(static_cast<unsigned>(v >> 32), &I[k], &U[k], &flags[k]);
+    if (w->wide)
+      fit_unpack_any(static_cast<unsigned>(v >> 32), &I[k], &U[k], &flags[k]);
+    else
+      fit_unpack(static_cast<unsigned>(v >> 32), &I[k], &U[k], &flags[k]);
   }
   return FSLR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fslr_match_reads(fslr_ctx* c, const fslr_params* p, const fslr_match_queries* q, uint32_t emit_mask,
+                     int64_t* row_off, int32_t* counts, int32_t* best, int64_t* n_rows) {
+  return match_run(c, false, p, nullptr, 0, q, emit_mask, row_off, counts, best, n_rows);
+}
+
+int fslr_match_reads_any(fslr_ctx* c, const fslr_params* p, const int32_t* umax, int32_t n_umax,
+                         const fslr_match_queries* q, uint32_t emit_mask, int64_t* row_off, int32_t* counts,
+                         int32_t* best, int64_t* n_rows) {
+  return match_run(c, true, p, umax, n_umax, q, emit_mask, row_off, counts, best, n_rows);
+}
+
+int fslr_match_rows(fslr_ctx* c, int32_t* partner, int32_t* I, int32_t* U, uint8_t* flags, int64_t capacity) {
+  return rows_out(c, false, partner, I, U, flags, capacity);
+}
+
+int fslr_match_rows_any(fslr_ctx* c, int32_t* partner, int32_t* I, int32_t* U, uint8_t* flags, int64_t capacity) {
+  return rows_out(c, true, partner, I, U, flags, capacity);
 }
 
 int fslr_match_timings(fslr_ctx* c, float* ms) {

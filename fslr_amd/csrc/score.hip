@@ -22,6 +22,14 @@
 // pair with I = U = 0 (the reference stops there).
 // Algorithmic bytes per pair: 8 B of ranks + 32 B of rmeta + 16 B x (L1 + L2) in,
 // 4 B out.
+//
+// fslr_score_pairs_any (reads of up to FSLR_MAX_ANY_L intervals): on a context without
+// virtual reads it is the driver and the kernel above.  On one with virtual reads k_score_pairs_any takes
+// real ranks: a read's list is its first chunk at rmeta[r].x and the rest from lg_off2[r], lg_rlen[r]
+// intervals in all.  A wave whose four pairs are all of two lists <= FSLR_MAX_L keeps the lane groups; a
+// wave that meets a longer pair runs its pairs one at a time on 64 lanes, the long ones through long_fit
+// (firstfit.hpp: list2 in chunks of 64 columns, one matched bit per row).  The result word is the wide one
+// (I | U << 13 | flags << 27) and EDGE beyond the pass table comes from the call's umax.
 #include <algorithm>
 #include <cstdint>
 #include <cstdlib>
@@ -38,9 +46,11 @@ using namespace fslr;
 // the scoring scratch (grows only, bounded by the chunk) and the last call's event times
 struct ScoreWork {
   int* ab = nullptr;                 // [2 x cap] the chunk's a, b
-  unsigned* out = nullptr;           // [cap] I | U << 8 | flags << 16
+  unsigned* out = nullptr;           // [cap] I | U << 8 | flags << 16; a virtual context's: I | U << 13 | flags << 27
   int64_t cap = 0;
   unsigned char* pt = nullptr;       // [FSLR_MAX_L x kPassStride] the pass table
+  int* umax = nullptr;               // [umax_cap] the _any call's cutoff table
+  int umax_cap = 0;
   unsigned* host = nullptr;          // [host_cap] pinned: the chunk's packed results
   int64_t host_cap = 0;
   hipEvent_t ev[4] = {};             // upload | kernel | download boundaries of a chunk
@@ -51,7 +61,7 @@ struct ScoreWork {
 void fslr_score_free(fslr_ctx* c) {
   ScoreWork* w = c->scw;
   if (!w) return;
-  void* bufs[] = {w->ab, w->out, w->pt};
+  void* bufs[] = {w->ab, w->out, w->pt, w->umax};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (w->host) (void)hipHostFree(w->host);
@@ -97,9 +107,10 @@ __device__ __forceinline__ PairMeta pair_meta(const ScoreArgs& s, int k, bool va
   return m;
 }
 
-// 64 / W pairs side by side, pair k on the W-lane group of this lane (valid: k is a pair)
+// 64 / W pairs side by side, the pair of meta m on the W-lane group of this lane (valid: it is a pair):
+// its first-fit
 template <int W>
-__device__ __forceinline__ void score_groups(const ScoreArgs& s, int k, bool valid, const PairMeta& m, int lane) {
+__device__ __forceinline__ FirstFit group_fit(const ScoreArgs& s, bool valid, const PairMeta& m, int lane) {
   const int l = lane & (W - 1);
   const int gbase = lane & ~(W - 1);
   const bool col = valid && l < m.LB;
@@ -132,7 +143,13 @@ __device__ __forceinline__ void score_groups(const ScoreArgs& s, int k, bool val
       ff.row<W>(c, si, ei, ti, r0 + i < m.LA, bj, col, lane);
     }
   }
-  if (valid && l == 0) s.out[k] = fit_result(m.LA, m.LB, ff.I, ff.zd, m.gate, s.pt);
+  return ff;
+}
+
+template <int W>
+__device__ __forceinline__ void score_groups(const ScoreArgs& s, int k, bool valid, const PairMeta& m, int lane) {
+  const FirstFit ff = group_fit<W>(s, valid, m, lane);
+  if (valid && (lane & (W - 1)) == 0) s.out[k] = fit_result(m.LA, m.LB, ff.I, ff.zd, m.gate, s.pt);
 }
 
 __global__ __launch_bounds__(256) void k_score_pairs(ScoreArgs s) {
@@ -161,6 +178,85 @@ __global__ __launch_bounds__(256) void k_score_pairs(ScoreArgs s) {
   }
 }
 
+// ---- real ranks on a context with virtual reads ------------------------------------------------------
+
+struct ScoreAnyArgs {
+  ScoreArgs s;                       // n_reads: the real reads
+  const int* rlen;                   // [n_real] a real read's interval count
+  const int* off2;                   // [n_real] where a long read's intervals beyond FSLR_MAX_L begin
+  const int* umax;
+  int n_umax;
+};
+
+struct AnyMeta {
+  PairMeta m;                        // offA, offB: the first chunks; LA, LB: the real lengths
+  int offA2, offB2;
+};
+
+__device__ __forceinline__ AnyMeta pair_meta_any(const ScoreAnyArgs& x, int k, bool valid) {
+  AnyMeta am{pair_meta(x.s, k, valid), 0, 0};
+  if (valid) {
+    const int ra = x.s.a[k], rb = x.s.b[k];
+    am.m.LA = x.rlen[ra];
+    am.m.LB = x.rlen[rb];
+    if (am.m.LA > FSLR_MAX_L) am.offA2 = x.off2[ra];
+    if (am.m.LB > FSLR_MAX_L) am.offB2 = x.off2[rb];
+  }
+  return am;
+}
+
+template <int W>
+__device__ __forceinline__ void score_groups_any(const ScoreAnyArgs& x, int k, bool valid, const PairMeta& m, int lane) {
+  const FirstFit ff = group_fit<W>(x.s, valid, m, lane);
+  if (valid && (lane & (W - 1)) == 0)
+    x.s.out[k] = fit_result_any(m.LA, m.LB, ff.I, ff.zd, m.gate, x.s.pt, x.umax, x.n_umax);
+}
+
+__global__ __launch_bounds__(256) void k_score_pairs_any(ScoreAnyArgs x) {
+  const ScoreArgs& s = x.s;
+  const int lane = threadIdx.x & 63;
+  const int nq = (s.n_pairs + 3) >> 2;
+  const int nw = gridDim.x * (blockDim.x >> 6);
+  for (int q = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); q < nq; q += nw) {
+    const int k0 = q << 2;
+    const int k = k0 + (lane >> 4);
+    const bool valid = k < s.n_pairs;
+    const AnyMeta am = pair_meta_any(x, k, valid);
+    const PairMeta& m = am.m;
+    if (__ballot(m.LA > FSLR_MAX_L || m.LB > FSLR_MAX_L) != 0) {
+      // a pair with a list beyond one wavefront of lanes: the wave's pairs one at a time
+      for (int p = 0; p < 4 && k0 + p < s.n_pairs; ++p) {
+        const AnyMeta a1 = pair_meta_any(x, k0 + p, true);
+        const PairMeta& m1 = a1.m;
+        if (m1.LA > FSLR_MAX_L || m1.LB > FSLR_MAX_L) {
+          int I = 0;
+          bool zd = false;
+          long_fit(m1.LA, m1.LB, ReadList{s.iv, m1.offA, a1.offA2, s.ni}, ReadList{s.iv, m1.offB, a1.offB2, s.ni}, lane,
+                   &I, &zd);
+          if (lane == 0) s.out[k0 + p] = fit_result_any(m1.LA, m1.LB, I, zd, m1.gate, s.pt, x.umax, x.n_umax);
+        } else {
+          score_groups_any<64>(x, k0 + p, true, m1, lane);
+        }
+      }
+      continue;
+    }
+    const bool w64 = s.wide || __ballot(m.LB > 32) != 0;
+    const bool w32 = __ballot(m.LB > 16) != 0;
+    if (w64) {
+      for (int p = 0; p < 4 && k0 + p < s.n_pairs; ++p)
+        score_groups_any<64>(x, k0 + p, true, pair_meta_any(x, k0 + p, true).m, lane);
+    } else if (w32) {
+      for (int p = 0; p < 4 && k0 + p < s.n_pairs; p += 2) {
+        const int k2 = k0 + p + (lane >> 5);
+        const bool v2 = k2 < s.n_pairs;
+        score_groups_any<32>(x, k2, v2, pair_meta_any(x, k2, v2).m, lane);
+      }
+    } else {
+      score_groups_any<16>(x, k, valid, m, lane);
+    }
+  }
+}
+
 int ensure_scratch(fslr_ctx* c, ScoreWork* w, int64_t n) {
   int rc;
   if (!w->pt && (rc = dalloc(c, &w->pt, kPassBytes))) return rc;
@@ -178,6 +274,82 @@ int ensure_scratch(fslr_ctx* c, ScoreWork* w, int64_t n) {
                              hipHostMallocDefault));
     w->host_cap = w->cap;
   }
+  return FSLR_OK;
+}
+
+// the checked batch of either entry point, chunk after chunk.  virt: the context holds virtual reads and the
+// ranks are real ones (k_score_pairs_any, the wide result word, umax); else the lane-group kernel alone
+int score_run(fslr_ctx* c, const fslr_params* p, bool virt, const int32_t* umax, int32_t n_umax, int64_t n_pairs,
+              const int32_t* a, const int32_t* b, int32_t* I, int32_t* U, uint8_t* flags) {
+  const int64_t n_reads = virt ? c->lg_n_real : c->n;
+  if (n_pairs == 0) return FSLR_OK;
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (!c->scw) c->scw = new ScoreWork();
+  ScoreWork* w = c->scw;
+  w->timed = false;
+  w->ms[0] = w->ms[1] = w->ms[2] = 0;
+  if (int rc = ensure_scratch(c, w, std::min(n_pairs, kChunk))) return rc;
+  const bool prof = c->profiling;
+  if (prof && !w->ev_ok) {
+    for (hipEvent_t& e : w->ev) HIP_TRY(c, hipEventCreate(&e));
+    w->ev_ok = true;
+  }
+  hipStream_t st = c->stream;
+  const char* wide = std::getenv("FSLR_SCORE_WIDE");       // the timing tool's comparison only
+  ScoreArgs s{c->rmeta, c->iv, w->pt, w->ab, w->ab + w->cap, w->out, 0, static_cast<int>(n_reads), static_cast<int>(c->ni),
+              p->qlen_cut, p->nal_cut, wide && wide[0] == '1'};
+  ScoreAnyArgs x{s, c->lg_rlen, c->lg_off2, nullptr, 0};
+  if (virt && umax) {
+    if (n_umax > w->umax_cap) {
+      w->umax_cap = 0;
+      if (int rc = dalloc(c, &w->umax, n_umax)) return rc;
+      w->umax_cap = n_umax;
+    }
+    HIP_TRY(c, hipMemcpyAsync(w->umax, umax, static_cast<size_t>(n_umax) * sizeof(int), hipMemcpyHostToDevice, st));
+    x.umax = w->umax, x.n_umax = n_umax;
+  }
+  int64_t step = w->cap;
+  // FSLR_SCORE_CHUNK (tests): a small launch chunk, so that a small batch spans several; anything but a
+  // positive number is refused
+  if (const char* e = std::getenv("FSLR_SCORE_CHUNK")) {
+    char* end = nullptr;
+    const long long v = std::strtoll(e, &end, 10);
+    if (end == e || *end != '\0' || v < 1)
+      return fail(c, FSLR_ERR_INVALID, std::string("FSLR_SCORE_CHUNK=") + e + " is not a positive pair count");
+    step = std::min<int64_t>(step, v);
+  }
+  for (int64_t k0 = 0; k0 < n_pairs; k0 += step) {
+    const int64_t m = std::min<int64_t>(step, n_pairs - k0);
+    const size_t mb = static_cast<size_t>(m) * sizeof(int);
+    if (prof) HIP_TRY(c, hipEventRecord(w->ev[0], st));
+    if (k0 == 0) HIP_TRY(c, hipMemcpyAsync(w->pt, p->pass_table, kPassBytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(w->ab, a + k0, mb, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(w->ab + w->cap, b + k0, mb, hipMemcpyHostToDevice, st));
+    if (prof) HIP_TRY(c, hipEventRecord(w->ev[1], st));
+    s.n_pairs = static_cast<int>(m);
+    if (virt) {
+      x.s.n_pairs = static_cast<int>(m);
+      k_score_pairs_any<<<grid_for((m + 3) / 4, 4, 256 * 32), 256, 0, st>>>(x);
+    } else {
+      k_score_pairs<<<grid_for((m + 3) / 4, 4, 256 * 32), 256, 0, st>>>(s);
+    }
+    HIP_TRY(c, hipGetLastError());
+    if (prof) HIP_TRY(c, hipEventRecord(w->ev[2], st));
+    HIP_TRY(c, hipMemcpyAsync(w->host, w->out, mb, hipMemcpyDeviceToHost, st));
+    if (prof) HIP_TRY(c, hipEventRecord(w->ev[3], st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if (virt)
+      for (int64_t k = 0; k < m; ++k) fit_unpack_any(w->host[k], &I[k0 + k], &U[k0 + k], &flags[k0 + k]);
+    else
+      for (int64_t k = 0; k < m; ++k) fit_unpack(w->host[k], &I[k0 + k], &U[k0 + k], &flags[k0 + k]);
+    if (prof)
+      for (int t = 0; t < 3; ++t) {
+        float ms = 0;
+        HIP_TRY(c, hipEventElapsedTime(&ms, w->ev[t], w->ev[t + 1]));
+        w->ms[t] += ms;
+      }
+  }
+  w->timed = prof;
   return FSLR_OK;
 }
 
@@ -202,47 +374,30 @@ int fslr_score_pairs(fslr_ctx* c, const fslr_params* p, int64_t n_pairs, const i
                                            "] = " + std::to_string(bad_a ? a[k] : b[k]) + " is outside [0, " +
                                            std::to_string(c->n) + ")");
   }
-  if (n_pairs == 0) return FSLR_OK;
-  HIP_TRY(c, hipSetDevice(c->device));
-  if (!c->scw) c->scw = new ScoreWork();
-  ScoreWork* w = c->scw;
-  w->timed = false;
-  w->ms[0] = w->ms[1] = w->ms[2] = 0;
-  if (int rc = ensure_scratch(c, w, std::min(n_pairs, kChunk))) return rc;
-  const bool prof = c->profiling;
-  if (prof && !w->ev_ok) {
-    for (hipEvent_t& e : w->ev) HIP_TRY(c, hipEventCreate(&e));
-    w->ev_ok = true;
+  return score_run(c, p, false, nullptr, 0, n_pairs, a, b, I, U, flags);
+}
+
+int fslr_score_pairs_any(fslr_ctx* c, const fslr_params* p, const int32_t* umax, int32_t n_umax, int64_t n_pairs,
+                         const int32_t* a, const int32_t* b, int32_t* I, int32_t* U, uint8_t* flags) {
+  if (!c) return FSLR_ERR_INVALID;
+  if (!p || !p->pass_table) return fail(c, FSLR_ERR_INVALID, "fslr_score_pairs_any: null params or pass_table");
+  if (n_pairs < 0) return fail(c, FSLR_ERR_INVALID, "fslr_score_pairs_any: negative pair count");
+  if (n_pairs && (!a || !b || !I || !U || !flags)) return fail(c, FSLR_ERR_INVALID, "fslr_score_pairs_any: null array");
+  if (!c->reads_set) return fail(c, FSLR_ERR_STATE, "fslr_score_pairs_any: fslr_set_reads first");
+  const bool virt = c->lg_set;
+  if (virt && (!umax || n_umax < c->lg_max_len))
+    return fail(c, FSLR_ERR_INVALID, "fslr_score_pairs_any: the context holds reads of more than " +
+                                         std::to_string(FSLR_MAX_L) + " intervals: umax must cover I up to the longest read (" +
+                                         std::to_string(c->lg_max_len) + ")");
+  const int64_t n_real = virt ? c->lg_n_real : c->n;
+  for (int64_t k = 0; k < n_pairs; ++k) {
+    const bool bad_a = a[k] < 0 || a[k] >= n_real;
+    if (bad_a || b[k] < 0 || b[k] >= n_real)
+      return fail(c, FSLR_ERR_INVALID, std::string("fslr_score_pairs_any: ") + (bad_a ? "a[" : "b[") + std::to_string(k) +
+                                           "] = " + std::to_string(bad_a ? a[k] : b[k]) + " is outside [0, " +
+                                           std::to_string(n_real) + ")");
   }
-  hipStream_t st = c->stream;
-  const char* wide = std::getenv("FSLR_SCORE_WIDE");       // the timing tool's comparison only
-  ScoreArgs s{c->rmeta, c->iv, w->pt, w->ab, w->ab + w->cap, w->out, 0, static_cast<int>(c->n), static_cast<int>(c->ni),
-              p->qlen_cut, p->nal_cut, wide && wide[0] == '1'};
-  for (int64_t k0 = 0; k0 < n_pairs; k0 += w->cap) {
-    const int64_t m = std::min<int64_t>(w->cap, n_pairs - k0);
-    const size_t mb = static_cast<size_t>(m) * sizeof(int);
-    if (prof) HIP_TRY(c, hipEventRecord(w->ev[0], st));
-    if (k0 == 0) HIP_TRY(c, hipMemcpyAsync(w->pt, p->pass_table, kPassBytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(w->ab, a + k0, mb, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(w->ab + w->cap, b + k0, mb, hipMemcpyHostToDevice, st));
-    if (prof) HIP_TRY(c, hipEventRecord(w->ev[1], st));
-    s.n_pairs = static_cast<int>(m);
-    k_score_pairs<<<grid_for((m + 3) / 4, 4, 256 * 32), 256, 0, st>>>(s);
-    HIP_TRY(c, hipGetLastError());
-    if (prof) HIP_TRY(c, hipEventRecord(w->ev[2], st));
-    HIP_TRY(c, hipMemcpyAsync(w->host, w->out, mb, hipMemcpyDeviceToHost, st));
-    if (prof) HIP_TRY(c, hipEventRecord(w->ev[3], st));
-    HIP_TRY(c, hipStreamSynchronize(st));
-    for (int64_t k = 0; k < m; ++k) fit_unpack(w->host[k], &I[k0 + k], &U[k0 + k], &flags[k0 + k]);
-    if (prof)
-      for (int t = 0; t < 3; ++t) {
-        float ms = 0;
-        HIP_TRY(c, hipEventElapsedTime(&ms, w->ev[t], w->ev[t + 1]));
-        w->ms[t] += ms;
-      }
-  }
-  w->timed = prof;
-  return FSLR_OK;
+  return score_run(c, p, virt, umax, n_umax, n_pairs, a, b, I, U, flags);
 }
 
 int fslr_score_timings(fslr_ctx* c, float* ms) {

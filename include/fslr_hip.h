@@ -585,7 +585,7 @@ int  fslr_search_timings(fslr_ctx *ctx, float *ms);
  * FSLR_ERR_STATE: no reads set.  FSLR_ERR_INVALID: a rank outside [0, n_reads) (the message names the
  * first offending position; nothing is written), or the context holds virtual reads (fslr_set_reads_any
  * with a read of more than FSLR_MAX_L intervals, fslr_set_long_reads): reads of more than FSLR_MAX_L
- * intervals are out of this call's scope.  Needs only the CSR: works with or without a built index,
+ * intervals are scored by fslr_score_pairs_any.  Needs only the CSR: works with or without a built index,
  * under a chromosome or position filter and with n_shards > 1.  The query state (edges, labels, degrees,
  * the cap, the ZeroDivisionError list, every error word) and the saved search batch are left alone.
  * Scratch grows on demand, bounded: a large batch is processed in chunks.
@@ -718,8 +718,8 @@ int  fslr_cluster_timings(fslr_ctx *ctx, float *ms);
  * FSLR_MATCH_SET: the distinct partners of one query read held in on-chip memory; a read with more is
  * still exact (its later hits are deduplicated against the staged hit list) but slower.
  * Out of scope: the edge cap (:223-224; a matched read's loop is not part of the resident graph's cap
- * replay, so every candidate is evaluated), query or resident reads of more than FSLR_MAX_L intervals,
- * matching through the multi-GPU split, and inserting matched reads into the index.
+ * replay, so every candidate is evaluated), matching through the multi-GPU split, and inserting matched
+ * reads into the index.  Query or resident reads of more than FSLR_MAX_L intervals: fslr_match_reads_any.
  * fslr_match_timings (fslr_set_profiling 1 or 2): HIP-event times (ms) of the last fslr_match_reads,
  * ms[0..3] = upload, search (count + fill), dedupe + score (+ row compaction), download, summed over its
  * blocks and chunks. */
@@ -739,6 +739,47 @@ int  fslr_match_reads(fslr_ctx *ctx, const fslr_params *params, const fslr_match
                       int64_t *row_off, int32_t *counts, int32_t *best, int64_t *n_rows);
 int  fslr_match_rows(fslr_ctx *ctx, int32_t *partner, int32_t *I, int32_t *U, uint8_t *flags, int64_t capacity);
 int  fslr_match_timings(fslr_ctx *ctx, float *ms);
+
+/* Pair scoring and read matching for reads of any length (1..FSLR_MAX_ANY_L intervals, the limit
+ * fslr_set_reads_any enforces).  fslr_score_pairs_any, fslr_match_reads_any and
+ * fslr_match_rows_any keep the contracts of fslr_score_pairs, fslr_match_reads and fslr_match_rows (the
+ * first-fit orientation list1 = a or the query read, the flags, ZD_OVERLAP giving I = U = 0, results at
+ * input positions, candidate first-visit order, exclude, emit_mask with its skipped first-fits, counts,
+ * best compared exactly with ties to the earlier candidate, the same bytes on every run, the state that is
+ * left alone, the bounded scratch, the chunking and FSLR_MATCH_BUDGET, the state errors) with four
+ * differences:
+ *   Rank space  a, b, exclude and partner are REAL read ranks in [0, n_real): the reads as the caller of
+ *               fslr_set_reads_any (or fslr_set_long_reads) numbered them; without virtual reads, every
+ *               uploaded read.  A resident read's list is its whole real list.  In matching a hit's
+ *               partner is the real read of the chunk it lies in, so the chunks of one long read, hit by
+ *               one or several query intervals, are one candidate, standing where its first hit stands;
+ *               the seen-set, exclude and FSLR_MATCH_SET count real reads.  A rank >= n_real (a virtual
+ *               chunk's rank) is FSLR_ERR_INVALID, named like any other bad rank; nothing is written.
+ *   Lengths     both lists may hold 1..FSLR_MAX_ANY_L intervals; a longer query read is FSLR_ERR_INVALID
+ *               (the message names it).  I (<= 4096) and U (<= 8191) are returned unclamped.
+ *   Cutoff      where I <= FSLR_MAX_L and U <= 2*FSLR_MAX_L, EDGE comes from pass_table as in the old
+ *               calls; elsewhere EDGE is GATE and I > 0 and U <= umax[I-1] (umax[i] = the largest passing
+ *               U for I = i + 1, i when none passes: the table fslr_set_long_cutoffs takes; make it for
+ *               max_i >= the longest list of either side, so that it reaches every U).  umax is a host
+ *               pointer, uploaded per call; the table of fslr_set_long_cutoffs is not touched.  It is
+ *               required when the context holds virtual reads or (matching) a query read has more than
+ *               FSLR_MAX_L intervals: non-NULL with n_umax >= the longest resident real read (I never
+ *               exceeds it); otherwise FSLR_ERR_INVALID before anything runs.  When neither holds it may
+ *               be NULL and is not looked at.
+ *   Tie ranks   (matching) where the reads came without iv_data_pos, a tied hit's data position is its
+ *               index in the real CSR, also under virtual reads.
+ * On a context without virtual reads and (matching) a batch without a query read of more than FSLR_MAX_L
+ * intervals, the _any calls run the very drivers and kernels of the old calls and return the same bytes.
+ * The saved batch of fslr_match_reads_any is read by fslr_match_rows_any alone and that of fslr_match_reads
+ * by fslr_match_rows alone (FSLR_ERR_STATE otherwise); either call replaces the other's batch.
+ * fslr_score_timings and fslr_match_timings report the last call of either kind. */
+#define FSLR_MAX_ANY_L 4096          /* max intervals per read of the _any calls and fslr_set_reads_any */
+int  fslr_score_pairs_any(fslr_ctx *ctx, const fslr_params *params, const int32_t *umax, int32_t n_umax,
+                          int64_t n_pairs, const int32_t *a, const int32_t *b, int32_t *I, int32_t *U, uint8_t *flags);
+int  fslr_match_reads_any(fslr_ctx *ctx, const fslr_params *params, const int32_t *umax, int32_t n_umax,
+                          const fslr_match_queries *queries, uint32_t emit_mask, int64_t *row_off, int32_t *counts,
+                          int32_t *best, int64_t *n_rows);
+int  fslr_match_rows_any(fslr_ctx *ctx, int32_t *partner, int32_t *I, int32_t *U, uint8_t *flags, int64_t capacity);
 
 /* Device-side views for collectives (e.g. RCCL all_gather of labels). */
 int  fslr_labels_device_ptr(fslr_ctx *ctx, void **dptr);
