@@ -141,7 +141,8 @@ typedef struct {
  *   SWEEP  one forward sweep over the sorted index meets every overlapping interval pair once;
  *          match entries are grouped per read and the greedy runs per pair (sweep.hip).  Needs
  *          overlap thresholds >= 1 (overlap > 0) and no aln_size == 0 interval; does not count
- *          evaluated_pairs / jaccard_evals (reported as -1).
+ *          evaluated_pairs / jaccard_evals (reported as -1).  It takes no read range: a forced
+ *          SWEEP evaluates the pairs of every read, whatever [a_begin, a_end) of fslr_query.
  *   AUTO   SWEEP when the input allows it and the query covers all reads, else WALK. */
 #define FSLR_ENGINE_AUTO 0
 #define FSLR_ENGINE_WALK 1
@@ -312,7 +313,8 @@ int  fslr_apply_edge_cap(fslr_ctx *ctx, int32_t edge_threshold, fslr_cap_stats *
 /* The same check without a host round trip, for a repeated query on unchanged input: the device ORs
  * (max forward degree > edge_threshold) | (a listed ZeroDivisionError pair) << 1 into a sticky word (async);
  * fslr_edge_cap_deferred_read syncs, returns the word and clears it.  A nonzero word means a step needed
- * fslr_apply_edge_cap (or raised): its results are to be recomputed synchronously. */
+ * fslr_apply_edge_cap (or raised): its results are to be recomputed synchronously.  FSLR_ERR_STATE on a
+ * context that never had reads set (no query can have run). */
 int  fslr_edge_cap_deferred(fslr_ctx *ctx, int32_t edge_threshold);
 int  fslr_edge_cap_deferred_read(fslr_ctx *ctx, int32_t *flags);
 /* cluster.py:230-234 — union-find over the edges: label = min rank in component.  Async.  Every query
