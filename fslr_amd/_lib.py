@@ -49,7 +49,7 @@ EXPORTED = ['fslr_abi_version', 'fslr_last_error', 'fslr_ctx_create', 'fslr_ctx_
             'fslr_cluster_table', 'fslr_get_cluster_ids', 'fslr_get_cluster_members', 'fslr_assign_clusters',
             'fslr_choose_representatives', 'fslr_cluster_timings',
             'fslr_match_reads', 'fslr_match_rows', 'fslr_match_timings', 'fslr_score_pairs_any',
-            'fslr_match_reads_any', 'fslr_match_rows_any']
+            'fslr_match_reads_any', 'fslr_match_rows_any', 'fslr_append_reads', 'fslr_append_timings']
 # fslr_score_pairs' flag bits (include/fslr_hip.h)
 SCORE_GATE, SCORE_EDGE, SCORE_ZD_GATE, SCORE_ZD_OVERLAP = 1, 2, 4, 8
 # fslr_coverage_*: keys per tile of the sorted arrays, queries per chunk (include/fslr_hip.h)
@@ -57,6 +57,8 @@ COVERAGE_TILE = 256
 COVERAGE_CHUNK = 1 << 21
 # fslr_match_reads: distinct partners of one query read held in on-chip memory (include/fslr_hip.h FSLR_MATCH_SET)
 MATCH_SET = 256
+# fslr_append_reads: outputs per tile of the merge kernel (include/fslr_hip.h FSLR_APPEND_TILE)
+APPEND_TILE = 1024
 
 
 class HipUnavailable(RuntimeError):
@@ -243,6 +245,8 @@ def load(path: str = LIB_PATH):
                                                 ctypes.c_uint32, vp, vp, vp, ctypes.POINTER(ctypes.c_int64)]),
         'fslr_match_rows_any': (ctypes.c_int, [vp, vp, vp, vp, vp, i64]),
         'fslr_match_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        'fslr_append_reads': (ctypes.c_int, [vp, ctypes.POINTER(Reads)]),
+        'fslr_append_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         'fslr_coverage_build': (ctypes.c_int, [vp, i64, i32, vp, vp, vp]),
         'fslr_coverage_at': (ctypes.c_int, [vp, i64, vp, vp, vp]),
         'fslr_coverage_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
@@ -453,6 +457,37 @@ class Context:
         # order (a caller-built list) takes the full (chrom, start) sort
         self.set_reads(csr.read_off, csr.read_qlen2, csr.read_nal, csr.iv_chrom, csr.iv_start, csr.iv_end, iv_thr,
                        csr.n_chroms, iv_data_pos=csr.data_pos if getattr(csr, 'start_sorted', True) else None)
+
+    def append_reads(self, read_off, read_qlen2, read_nal, iv_chrom, iv_start, iv_end, iv_thr, n_chroms, iv_data_pos):
+        """fslr_append_reads: m more reads behind the resident ones (ranks n .., the resident dense chromosome
+        ids, ``iv_data_pos`` the batch's own start-sorted order).  A refused batch leaves the context as it
+        was; after a successful one build_index again."""
+        arrs = [np.ascontiguousarray(x, dtype=np.int32) for x in
+                (read_off, read_qlen2, read_nal, iv_chrom, iv_start, iv_end, iv_thr)]
+        dp = None if iv_data_pos is None else np.ascontiguousarray(iv_data_pos, dtype=np.int32)
+        r = Reads(len(arrs[1]), len(arrs[3]), int(n_chroms), *(_ptr(a) for a in arrs),
+                  _ptr(dp) if dp is not None else None)
+        rc = self._L.fslr_append_reads(self._h, ctypes.byref(r))
+        if rc == FSLR_ERR_HIP:
+            # a refused batch (FSLR_ERR_INVALID / FSLR_ERR_STATE) and a failed allocation (FSLR_ERR_NOMEM) leave
+            # the context as it was; a device failure may leave no reads set (include/fslr_hip.h)
+            self.n_reads = self.n_intervals = 0
+        self._check(rc)
+        self.n_reads += len(arrs[1])
+        self.n_intervals += len(arrs[3])
+        if len(arrs[1]):
+            self.thr_gen = getattr(self, 'thr_gen', 0) + 1        # the device's threshold column changed
+
+    def append_csr(self, csr, iv_thr):
+        """append_reads of a ``fslr_amd.prep.CSR`` whose ``iv_chrom`` holds the resident dense ids."""
+        self.append_reads(csr.read_off, csr.read_qlen2, csr.read_nal, csr.iv_chrom, csr.iv_start, csr.iv_end, iv_thr,
+                          csr.n_chroms, csr.data_pos)
+
+    def append_timings(self) -> dict:
+        """HIP-event times (ms) of the last append_reads' phases (profiling contexts)."""
+        ms = (ctypes.c_float * 4)()
+        self._check(self._L.fslr_append_timings(self._h, ms))
+        return dict(zip(('upload', 'pack', 'merge', 'total'), (float(x) for x in ms)))
 
     def set_thresholds(self, iv_thr):
         t = np.ascontiguousarray(iv_thr, dtype=np.int32)

@@ -524,6 +524,94 @@ class DeviceIntervalIndex:
             self.ctx.load_csr(c, thr0)
         self.ctx.build_index()
 
+    # -- more reads for the resident set (fslr_append_reads) ------------------------
+    def append(self, new_data):
+        """Add the reads of ``new_data`` (prepare_data's result for the new rows, or the reference's item
+        list) to the resident set on the device and rebuild the index.  The resident reads keep their ranks,
+        the new ones follow in the order of ``build_csr(new_data)``; the `data` list becomes the stable merge
+        of the two start-sorted lists (resident first on equal starts).  Only the new reads' columns go to
+        the device; the host mirrors (``data``, ``csr``) are rebuilt by numpy concatenation, O(n + m).
+        Afterwards ``self.data`` (also ``self.source``) is the merged IntervalData and ``self.csr`` the
+        concatenated CSR with the merged data positions.  A read is a whole list: a qname that is already
+        resident raises ValueError.  Chromosome values the index has not seen take the next dense ids in
+        ascending value."""
+        if self.long is not None:
+            raise NotImplementedError(f'append does not take an index with reads of more than {FSLR_MAX_L} intervals')
+        if not isinstance(new_data, IntervalData):
+            new_data = IntervalData.from_items(new_data)
+        old, oc = self.data, self.csr
+        if old.chrom.dtype.kind not in 'iu' or new_data.chrom.dtype.kind not in 'iu':
+            raise TypeError('append needs numeric chromosome values (rename_chromosomes)')
+        if not getattr(oc, 'start_sorted', True):
+            raise ValueError('append needs an index built from a start-sorted data list')
+        nc = build_csr(new_data)
+        if not nc.start_sorted:
+            raise ValueError('the new data list is not in start order (prepare_data sorts it)')
+        if has_long_reads(nc):
+            raise NotImplementedError(f'append does not take a read of more than {FSLR_MAX_L} intervals')
+        names = lambda q: q if isinstance(q, np.ndarray) else q[np.arange(len(q))]
+        old_names, new_names = names(old.qnames), names(new_data.qnames)
+        resident = set(old_names[np.asarray(oc.read_qcode, np.int64)].tolist())
+        twice = [q for q in new_names[np.asarray(nc.read_qcode, np.int64)].tolist() if q in resident]
+        if twice:
+            raise ValueError(f'{twice[0]!r} is already a read of this index (a read is a whole list and is never '
+                             f'extended); {len(twice)} such qname(s)')
+        # the batch's raw chromosome values -> the resident dense ids, unseen values behind them
+        keys, ids, _ = self._chrom_table()
+        raw = np.asarray(new_data.chrom, np.int64)[np.asarray(nc.data_pos, np.int64)]
+        keys = np.zeros(0, np.int64) if keys is None else keys
+        unseen = np.setdiff1d(raw, keys)                                  # sorted, unique
+        all_keys = np.concatenate([keys, unseen])
+        all_ids = np.concatenate([np.asarray(ids, np.int64) if keys.size else np.zeros(0, np.int64),
+                                  oc.n_chroms + np.arange(unseen.size, dtype=np.int64)])
+        o = np.argsort(all_keys, kind='stable')
+        dense = all_ids[o][np.searchsorted(all_keys[o], raw)].astype(np.int32) if raw.size else np.zeros(0, np.int32)
+        n_chroms = int(oc.n_chroms + unseen.size)
+        batch = CSR(read_off=nc.read_off, read_qlen2=nc.read_qlen2, read_nal=nc.read_nal, iv_chrom=dense,
+                    iv_start=nc.iv_start, iv_end=nc.iv_end, iv_aln=nc.iv_aln, n_chroms=n_chroms,
+                    read_qcode=nc.read_qcode, data_pos=nc.data_pos, nal_varies=nc.nal_varies)
+        # the host mirrors first (where each element of either list lands in the merged list): should
+        # making them fail, the device still holds what self.data and self.csr describe
+        a, b = np.asarray(old.start, np.int64), np.asarray(new_data.start, np.int64)
+        pos_old = np.arange(a.size, dtype=np.int64) + np.searchsorted(b, a, side='left')
+        pos_new = np.arange(b.size, dtype=np.int64) + np.searchsorted(a, b, side='right')
+
+        def merged(x, y):
+            x, y = np.asarray(x), np.asarray(y)
+            out = np.empty(x.size + y.size, np.result_type(x.dtype, y.dtype))
+            out[pos_old], out[pos_new] = x, y
+            return out
+        cols = {f: merged(getattr(old, f), getattr(new_data, f))
+                for f in ('chrom', 'start', 'end', 'aln_size', 'n_alignments', 'qlen2', 'middle', 'index')}
+        data = IntervalData(qcode=merged(old.qcode, np.asarray(new_data.qcode, np.int64) + len(old_names)),
+                            qnames=np.concatenate([old_names, new_names]), **cols)
+        cat = lambda f: np.concatenate([getattr(oc, f), getattr(batch, f)])
+        data._csr = CSR(read_off=np.concatenate([oc.read_off, oc.n_intervals + nc.read_off[1:]]).astype(np.int32),
+                        read_qlen2=cat('read_qlen2'), read_nal=cat('read_nal'), iv_chrom=cat('iv_chrom'),
+                        iv_start=cat('iv_start'), iv_end=cat('iv_end'), iv_aln=cat('iv_aln'), n_chroms=n_chroms,
+                        read_qcode=np.concatenate([oc.read_qcode, np.asarray(nc.read_qcode, np.int64) + len(old_names)]),
+                        data_pos=np.concatenate([pos_old[np.asarray(oc.data_pos, np.int64)],
+                                                 pos_new[np.asarray(nc.data_pos, np.int64)]]),
+                        nal_varies=bool(oc.nal_varies or nc.nal_varies), start_sorted=True)
+        # the batch goes up folded for the overlap score_pairs / match_reads last installed, if those
+        # thresholds are still the device's (they key their skip of set_thresholds on _thr_key); otherwise
+        # with placeholders, and the next call folds every threshold as after a fresh upload
+        ctx = self.ctx
+        key = self.__dict__.get('_thr_key')
+        live = key is not None and key[1] == getattr(ctx, 'thr_gen', 0)
+        self.__dict__.pop('_thr_key', None)
+        thr = fold_overlap_threshold(nc.iv_aln, key[0]) if live else \
+            np.where(nc.iv_aln == 0, FSLR_THR_ZERO_ALN, 0).astype(np.int32)
+        ctx.append_csr(batch, thr)
+        self.source = self.data = data
+        self.csr = data._csr
+        self.__dict__.pop('_ctable', None)
+        self.__dict__.pop('_rank_of', None)
+        if live:
+            self._thr_key = (key[0], ctx.thr_gen)
+        ctx.build_index()
+        return self
+
     # -- search (cluster.py:201: tree[itv.chrom].search_values(itv.start, itv.end)) ----------------
     # A query (chrom, start, end) hits the stored interval (c, s, e) iff c == chrom, s <= end and
     # e >= start (end-inclusive, superintervals search_values).  Hits are positions in the `data` list
@@ -836,6 +924,11 @@ class RowsIndex(DeviceIntervalIndex):
         self.overlap = float(overlap)
         ctx.build_index()
 
+    def append(self, new_data):
+        raise NotImplementedError('an index made from rows on the device (fslr_set_reads_rows) does not append: '
+                                  'fslr_append_reads extends reads set by fslr_set_reads; build the index from '
+                                  'prepare_data\'s result to append to it')
+
 
 class MultiGpuIndex:
     """What build_interval_trees returns for ``n_gpus > 1``: the prepared CSR on the host.  The ranks
@@ -862,6 +955,10 @@ class MultiGpuIndex:
                                   'build it with n_gpus=1 to score pairs')
 
     score_pairs_any = score_pairs
+
+    def append(self, *args, **kwargs):
+        raise NotImplementedError('a multi-GPU index lives in the rank processes and does not append '
+                                  '(fslr_append_reads needs the whole index on one context); build it with n_gpus=1')
 
     def match_reads_any(self, *args, **kwargs):
         return self.match_reads(*args, **kwargs)

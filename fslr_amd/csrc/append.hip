@@ -1,0 +1,434 @@
+// append.hip — fslr_append_reads: more reads for a resident set, on the device.
+//
+// The batch's columns go up as they are (m reads, mi intervals: the only H2D traffic), are validated and
+// packed in scratch by upload.hip's kernels with the ranks based at n and the CSR offsets at ni, and nothing
+// resident is written until every check has passed.  Then the batch's rows are copied behind the resident
+// CSR and the two start-sorted data lists are merged (k_append_merge, a merge-path: the resident element
+// first on equal starts) into a second set of data-order buffers, which is swapped in; one gather rewrites
+// the data positions.  No global atomic decides where anything lands: the same bytes on every run, and the
+// bytes fslr_set_reads gives for the concatenated CSR with the merged iv_data_pos.
+#include <algorithm>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "fslr_hip.h"
+#include "ctx.hpp"
+#include "kernels.hpp"
+
+using namespace fslr;
+
+struct AppendWork {
+  int* cols = nullptr;               // the batch's columns as copied: off, qlen2, nal | chrom, start, end, thr, data_pos
+  int64_t cols_cap = 0;
+  int4* rmeta = nullptr;             // [m] packed reads (ranks n .., offsets ni ..)
+  unsigned char* rlen8 = nullptr;
+  int64_t m_cap = 0;
+  int4* iv = nullptr;                // [mi] packed intervals, the batch's CSR order
+  int* inv = nullptr;                // [mi] data position -> CSR index (the permutation check)
+  unsigned* dch = nullptr;           // [mi] the batch's own start-sorted data list
+  int4* drc = nullptr;
+  int2* dgt = nullptr;
+  int64_t mi_cap = 0;
+  unsigned long long* w64 = nullptr; // [n_chroms + 2] intervals per chromosome, first failures
+  int64_t w64_cap = 0;
+  unsigned* alt_ch = nullptr;        // the second set of data-order buffers (merge output; swapped with the context's)
+  int4* alt_rec = nullptr;
+  int2* alt_gate = nullptr;
+  int64_t alt_cap = 0;
+  hipEvent_t ev[5] = {};             // start | uploaded | packed | merge start | merge end
+  bool ev_ok = false, timed = false;
+  float ms[4] = {0, 0, 0, 0};        // upload, validate + pack, merge, total
+};
+
+void fslr_append_free(fslr_ctx* c) {
+  AppendWork* w = c->apw;
+  if (!w) return;
+  void* bufs[] = {w->cols, w->rmeta, w->rlen8, w->iv, w->inv, w->dch, w->drc, w->dgt, w->w64, w->alt_ch, w->alt_rec, w->alt_gate};
+  for (void* b : bufs)
+    if (b) (void)hipFree(b);
+  if (w->ev_ok)
+    for (hipEvent_t& e : w->ev) (void)hipEventDestroy(e);
+  delete w;
+  c->apw = nullptr;
+}
+
+namespace {
+
+constexpr int kTile = FSLR_APPEND_TILE;
+
+// Stable merge of the resident data list R (ni elements) and the batch's N (mi), both sorted by start
+// (rec.x), the resident element first on equal starts.  A block takes output tiles of kTile elements: the
+// split of each tile end on its diagonal by binary search (the first i with R[i].x > N[d - 1 - i].x), then
+//   - a tile of one list alone is a straight copy (with m << n nearly every tile): 16-B records, 8-B gate
+//     words and 4-B chromosomes, consecutive lanes on consecutive elements;
+//   - a mixed tile stages its keys in LDS, ranks every element against the other list's run there, and
+//     writes its outputs in order from the source index each output position recorded.
+// newpos[i] (i < ni) = the merged position of resident data position i, newpos[ni + j] that of the batch's j.
+__global__ __launch_bounds__(256) void k_append_merge(const unsigned* __restrict__ rch, const int4* __restrict__ rrec,
+                                                      const int2* __restrict__ rgate, int ni,
+                                                      const unsigned* __restrict__ nch, const int4* __restrict__ nrec,
+                                                      const int2* __restrict__ ngate, int mi,
+                                                      unsigned* __restrict__ och, int4* __restrict__ orec,
+                                                      int2* __restrict__ ogate, int* __restrict__ newpos) {
+  __shared__ int split[2];
+  __shared__ int key[kTile];
+  __shared__ int src[kTile];
+  const long long total = static_cast<long long>(ni) + mi;
+  const int tid = threadIdx.x;
+  for (long long tile = blockIdx.x; tile * kTile < total; tile += gridDim.x) {
+    const int d0 = static_cast<int>(tile * kTile);
+    const int d1 = static_cast<int>(std::min<long long>(tile * kTile + kTile, total));
+    if (tid < 2) {
+      const int d = tid ? d1 : d0;
+      int lo = std::max(0, d - mi), hi = std::min(d, ni);
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        FSLR_BOUND(mid, ni);
+        FSLR_BOUND(d - 1 - mid, mi);
+        if (rrec[mid].x <= nrec[d - 1 - mid].x) lo = mid + 1;
+        else hi = mid;
+      }
+      split[tid] = lo;
+    }
+    __syncthreads();
+    const int i0 = split[0], i1 = split[1];
+    const int j0 = d0 - i0, j1 = d1 - i1;
+    const int na = i1 - i0, nb = j1 - j0, len = d1 - d0;
+    if (nb == 0) {
+      for (int t = tid; t < len; t += blockDim.x) {
+        FSLR_BOUND(i0 + t, ni);
+        FSLR_BOUND(d0 + t, total);
+        orec[d0 + t] = rrec[i0 + t];
+        ogate[d0 + t] = rgate[i0 + t];
+        och[d0 + t] = rch[i0 + t];
+        newpos[i0 + t] = d0 + t;
+      }
+    } else if (na == 0) {
+      for (int t = tid; t < len; t += blockDim.x) {
+        FSLR_BOUND(j0 + t, mi);
+        FSLR_BOUND(d0 + t, total);
+        orec[d0 + t] = nrec[j0 + t];
+        ogate[d0 + t] = ngate[j0 + t];
+        och[d0 + t] = nch[j0 + t];
+        newpos[ni + j0 + t] = d0 + t;
+      }
+    } else {
+      for (int t = tid; t < len; t += blockDim.x) {
+        if (t < na) {
+          FSLR_BOUND(i0 + t, ni);
+          key[t] = rrec[i0 + t].x;
+        } else {
+          FSLR_BOUND(j0 + t - na, mi);
+          key[t] = nrec[j0 + t - na].x;
+        }
+      }
+      __syncthreads();
+      for (int t = tid; t < len; t += blockDim.x) {
+        const int k = key[t];
+        int pos;
+        if (t < na) {                      // + the batch's elements of this tile with a start < k
+          int lo = na, hi = len;
+          while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (key[mid] < k) lo = mid + 1;
+            else hi = mid;
+          }
+          pos = t + (lo - na);
+          newpos[i0 + t] = d0 + pos;
+        } else {                           // + the resident elements of this tile with a start <= k
+          int lo = 0, hi = na;
+          while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (key[mid] <= k) lo = mid + 1;
+            else hi = mid;
+          }
+          pos = (t - na) + lo;
+          FSLR_BOUND(ni + j0 + t - na, total);
+          newpos[ni + j0 + t - na] = d0 + pos;
+        }
+        FSLR_BOUND(pos, len);
+        src[pos] = t;
+      }
+      __syncthreads();
+      for (int p = tid; p < len; p += blockDim.x) {
+        const int t = src[p];
+        FSLR_BOUND(t, len);
+        FSLR_BOUND(d0 + p, total);
+        if (t < na) {
+          FSLR_BOUND(i0 + t, ni);
+          orec[d0 + p] = rrec[i0 + t];
+          ogate[d0 + p] = rgate[i0 + t];
+          och[d0 + p] = rch[i0 + t];
+        } else {
+          FSLR_BOUND(j0 + t - na, mi);
+          orec[d0 + p] = nrec[j0 + t - na];
+          ogate[d0 + p] = ngate[j0 + t - na];
+          och[d0 + p] = nch[j0 + t - na];
+        }
+      }
+    }
+    __syncthreads();                       // split, key and src serve the block's next tile
+  }
+}
+
+// data_pos (CSR order) after the merge: a resident interval follows its old data position, a new one the
+// position in its own list
+__global__ void k_append_datapos(int* __restrict__ data_pos, int ni, const int* __restrict__ dp_new, int mi,
+                                 const int* __restrict__ newpos) {
+  const long long total = static_cast<long long>(ni) + mi;
+  for (long long k = blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x; k < total;
+       k += static_cast<long long>(gridDim.x) * blockDim.x) {
+    int at;
+    if (k < ni) {
+      at = data_pos[k];
+      FSLR_BOUND(at, ni);
+    } else {
+      const int e = dp_new[k - ni];
+      FSLR_BOUND(e, mi);
+      at = ni + e;
+    }
+    data_pos[k] = newpos[at];
+  }
+}
+
+int ensure_batch(fslr_ctx* c, AppendWork* w, int64_t m, int64_t mi, int n_chroms) {
+  int rc;
+  const int64_t cols = 3 * m + 1 + 5 * mi;
+  if (cols > w->cols_cap) {
+    w->cols_cap = 0;                             // (a failed growth leaves no buffer behind its capacity)
+    if ((rc = dalloc(c, &w->cols, static_cast<size_t>(cols + cols / 4)))) return rc;
+    w->cols_cap = cols + cols / 4;
+  }
+  if (m > w->m_cap) {
+    w->m_cap = 0;
+    if ((rc = dalloc(c, &w->rmeta, static_cast<size_t>(m + m / 4))) || (rc = dalloc(c, &w->rlen8, static_cast<size_t>(m + m / 4))))
+      return rc;
+    w->m_cap = m + m / 4;
+  }
+  if (mi > w->mi_cap) {
+    w->mi_cap = 0;
+    const size_t cap = static_cast<size_t>(mi + mi / 4);
+    if ((rc = dalloc(c, &w->iv, cap)) || (rc = dalloc(c, &w->inv, cap)) || (rc = dalloc(c, &w->dch, cap)) ||
+        (rc = dalloc(c, &w->drc, cap)) || (rc = dalloc(c, &w->dgt, cap)))
+      return rc;
+    w->mi_cap = static_cast<int64_t>(cap);
+  }
+  if (n_chroms + 2 > w->w64_cap) {
+    w->w64_cap = 0;
+    if ((rc = dalloc(c, &w->w64, static_cast<size_t>(n_chroms + 2)))) return rc;
+    w->w64_cap = n_chroms + 2;
+  }
+  return FSLR_OK;
+}
+
+// once memory is there nothing but the device can fail; what is then half written is not a set of reads
+int broken(fslr_ctx* c, int rc) {
+  c->reads_set = false;
+  c->index_built = false;
+  return rc;
+}
+
+#define APP_TRY(ctx, expr)                                                                                    \
+  do {                                                                                                        \
+    hipError_t e_ = (expr);                                                                                   \
+    if (e_ != hipSuccess)                                                                                     \
+      return broken((ctx), fail((ctx), FSLR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)));     \
+  } while (0)
+
+}  // namespace
+
+extern "C" {
+
+int fslr_append_reads(fslr_ctx* c, const fslr_reads* r) {
+  if (!c || !r) return FSLR_ERR_INVALID;
+  if (!c->reads_set) return fail(c, FSLR_ERR_STATE, "fslr_append_reads: no reads set (fslr_set_reads first)");
+  if (c->rows_set)
+    return fail(c, FSLR_ERR_STATE, "fslr_append_reads: the reads were made from rows (fslr_set_reads_rows), which it does not extend");
+  if (c->lg_set || !c->lg_perm.empty())
+    return fail(c, FSLR_ERR_STATE, "fslr_append_reads: the context holds virtual reads (fslr_set_reads_any / fslr_set_long_reads: "
+                                   "reads of more than " + std::to_string(FSLR_MAX_L) + " intervals), which it does not extend");
+  if (!c->have_data_pos)
+    return fail(c, FSLR_ERR_STATE, "fslr_append_reads: the reads were set without iv_data_pos (no start-sorted data list to merge into)");
+  if (c->n_shards > 1) return fail(c, FSLR_ERR_STATE, "fslr_append_reads: n_shards > 1 (fslr_set_shard): multi-GPU contexts do not append");
+  if (c->filter_active || c->pf_on)
+    return fail(c, FSLR_ERR_STATE, "fslr_append_reads: a chromosome or position filter is active");
+  const int64_t n = c->n, ni = c->ni, m = r->n_reads, mi = r->n_intervals;
+  if (m < 0 || mi < 0 || n + m >= FSLR_MAX_READS || ni + mi >= (int64_t(1) << 31) - 1)
+    return fail(c, FSLR_ERR_INVALID, "read / interval count out of range");
+  if (r->n_chroms < 1 || r->n_chroms >= (1 << 24)) return fail(c, FSLR_ERR_INVALID, "n_chroms out of range");
+  if (r->n_chroms < c->n_chroms) return fail(c, FSLR_ERR_INVALID, "fslr_append_reads: n_chroms below the resident value");
+  if (!r->read_off || !r->read_qlen2 || !r->read_nal || !r->iv_chrom || !r->iv_start || !r->iv_end || !r->iv_thr)
+    return fail(c, FSLR_ERR_INVALID, "null array");
+  if (!r->iv_data_pos) return fail(c, FSLR_ERR_INVALID, "fslr_append_reads: iv_data_pos is required");
+  if (r->read_off[0] != 0 || r->read_off[m] != mi) return fail(c, FSLR_ERR_INVALID, "read_off does not span intervals");
+  if (m == 0) return FSLR_OK;                    // nothing to add: no generation moves
+  HIP_TRY(c, hipSetDevice(c->device));
+  if (!c->apw) c->apw = new AppendWork();
+  AppendWork* w = c->apw;
+  w->timed = false;
+  const bool prof = c->profiling;
+  if (prof && !w->ev_ok) {
+    for (hipEvent_t& e : w->ev) HIP_TRY(c, hipEventCreate(&e));
+    w->ev_ok = true;
+  }
+  if (int rc = ensure_batch(c, w, m, mi, r->n_chroms)) return rc;
+  hipStream_t st = c->stream;
+  // ---- the batch: up as it is, validated and packed in scratch; nothing resident is written ----------
+  int* d_off = w->cols;
+  int* d_q2 = d_off + m + 1;
+  int* d_nal = d_q2 + m;
+  int* d_ch = d_nal + m;
+  int* d_st = d_ch + mi;
+  int* d_en = d_st + mi;
+  int* d_th = d_en + mi;
+  int* d_dp = d_th + mi;
+  unsigned long long* d_cnt = w->w64;
+  unsigned long long* d_err = w->w64 + r->n_chroms;
+  const size_t mb = static_cast<size_t>(m) * sizeof(int), ib = static_cast<size_t>(mi) * sizeof(int);
+  if (prof) HIP_TRY(c, hipEventRecord(w->ev[0], st));
+  HIP_TRY(c, hipMemsetAsync(d_cnt, 0, static_cast<size_t>(r->n_chroms) * sizeof(unsigned long long), st));
+  HIP_TRY(c, hipMemsetAsync(d_err, 0xff, 2 * sizeof(unsigned long long), st));
+  HIP_TRY(c, hipMemcpyAsync(d_off, r->read_off, mb + sizeof(int), hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_q2, r->read_qlen2, mb, hipMemcpyHostToDevice, st));
+  HIP_TRY(c, hipMemcpyAsync(d_nal, r->read_nal, mb, hipMemcpyHostToDevice, st));
+  if (mi) {
+    HIP_TRY(c, hipMemcpyAsync(d_ch, r->iv_chrom, ib, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(d_st, r->iv_start, ib, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(d_en, r->iv_end, ib, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(d_th, r->iv_thr, ib, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(d_dp, r->iv_data_pos, ib, hipMemcpyHostToDevice, st));
+  }
+  if (prof) HIP_TRY(c, hipEventRecord(w->ev[1], st));
+  // the reads' own checks on the host, in index order (fslr_set_reads' codes: 3 length, 4 n_alignments, 5 qlen2)
+  int bad = 0;
+  for (int64_t i = 0; i < m && !bad; ++i) {
+    const int len = r->read_off[i + 1] - r->read_off[i];
+    if (len < 1 || len > FSLR_MAX_L) bad = 3;
+    else if (r->read_nal[i] < 0 || r->read_nal[i] >= (1 << 24)) bad = 4;
+    else if (r->read_qlen2[i] < 0) bad = 5;
+  }
+  UploadArgs ua{};
+  ua.off = d_off;
+  ua.qlen2 = d_q2;
+  ua.nal = d_nal;
+  ua.chrom = d_ch;
+  ua.start = d_st;
+  ua.end = d_en;
+  ua.thr = d_th;
+  ua.dp = d_dp;
+  ua.n = static_cast<int>(m);
+  ua.ni = static_cast<int>(mi);
+  ua.n_chroms = r->n_chroms;
+  ua.reads_ok = bad == 0;
+  ua.rank_base = static_cast<int>(n);
+  ua.off_base = static_cast<int>(ni);
+  ua.iv = w->iv;
+  ua.rmeta = w->rmeta;
+  ua.rlen8 = w->rlen8;
+  ua.dch = w->dch;
+  ua.drc = w->drc;
+  ua.dgt = w->dgt;
+  ua.inv = w->inv;
+  ua.chrom_cnt = d_cnt;
+  ua.err = d_err;
+  HIP_TRY(c, launch_upload_pack(ua, st));
+  if (prof) HIP_TRY(c, hipEventRecord(w->ev[2], st));
+  int tmode = 0, any_zero = 0;
+  for (int64_t k = 0; k < mi; ++k) {
+    any_zero |= r->iv_thr[k] == FSLR_THR_ZERO_ALN;
+    tmode |= r->iv_thr[k] != FSLR_THR_ZERO_ALN && r->iv_thr[k] < 1;
+  }
+  std::vector<int64_t> batch_counts(static_cast<size_t>(r->n_chroms), 0);
+  unsigned long long err[2] = {0, 0};
+  HIP_TRY(c, hipMemcpyAsync(batch_counts.data(), d_cnt, batch_counts.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipMemcpyAsync(err, d_err, sizeof(err), hipMemcpyDeviceToHost, st));
+  HIP_TRY(c, hipStreamSynchronize(st));
+  if (err[0] != ~0ull) {
+    if ((err[0] & 7) == kUpErrChrom) return fail(c, FSLR_ERR_INVALID, "chrom id out of range");
+    return fail(c, FSLR_ERR_INVALID, "interval coordinates out of [0, 2^30)");
+  }
+  if (bad == 3) return fail(c, FSLR_ERR_INVALID, "every read needs 1.." + std::to_string(FSLR_MAX_L) + " intervals");
+  if (bad == 4) return fail(c, FSLR_ERR_INVALID, "n_alignments outside [0, 2^24)");
+  if (bad == 5) return fail(c, FSLR_ERR_INVALID, "qlen2 < 0");
+  if (err[1] != ~0ull) return fail(c, FSLR_ERR_INVALID, "iv_data_pos is not a start-sorted permutation");
+  // ---- room: the merge output first (a failure here leaves the context as it was) --------------------
+  const int64_t need_n = n + m, need_ni = ni + mi;
+  const int64_t cap_n = need_n > c->cap_n ? std::max(need_n, c->cap_n + c->cap_n / 2) : c->cap_n;
+  const int64_t cap_ni = need_ni > c->cap_ni ? std::max(need_ni, c->cap_ni + c->cap_ni / 2) : c->cap_ni;
+  const int64_t old_cap_ni = c->cap_ni;
+  if (w->alt_cap < cap_ni) {
+    w->alt_cap = 0;
+    int rc;
+    const size_t cap = static_cast<size_t>(cap_ni);
+    if ((rc = dalloc(c, &w->alt_ch, cap)) || (rc = dalloc(c, &w->alt_rec, cap)) || (rc = dalloc(c, &w->alt_gate, cap))) return rc;
+    w->alt_cap = cap_ni;
+  }
+  // ... and every buffer that has to grow, allocated before any is freed (the same holds for a failure here)
+  if (int rc = grow_capacity_keep(c, cap_n, cap_ni, r->n_chroms)) return rc;
+  // from here the index scratch is reused and the resident buffers are written
+  c->index_built = false;
+  c->hooked = false;
+  if (prof) APP_TRY(c, hipEventRecord(w->ev[3], st));
+  APP_TRY(c, hipMemcpyAsync(c->rmeta + n, w->rmeta, static_cast<size_t>(m) * sizeof(int4), hipMemcpyDeviceToDevice, st));
+  APP_TRY(c, hipMemcpyAsync(c->rlen8 + n, w->rlen8, static_cast<size_t>(m), hipMemcpyDeviceToDevice, st));
+  if (mi) APP_TRY(c, hipMemcpyAsync(c->iv + ni, w->iv, static_cast<size_t>(mi) * sizeof(int4), hipMemcpyDeviceToDevice, st));
+  int* newpos = c->vals;                         // [ni + mi] index-build scratch (the index is rebuilt anyway)
+  const int64_t tiles = (need_ni + kTile - 1) / kTile;
+  if (need_ni) {
+    k_append_merge<<<static_cast<int>(std::min<int64_t>(tiles, 256 * 16)), 256, 0, st>>>(
+        c->dchrom, c->drec, c->dgate, static_cast<int>(ni), w->dch, w->drc, w->dgt, static_cast<int>(mi), w->alt_ch,
+        w->alt_rec, w->alt_gate, newpos);
+    k_append_datapos<<<grid_for(need_ni), 256, 0, st>>>(c->data_pos, static_cast<int>(ni), d_dp, static_cast<int>(mi), newpos);
+    APP_TRY(c, hipGetLastError());
+  }
+  if (prof) APP_TRY(c, hipEventRecord(w->ev[4], st));
+  // chromosome ranges of the (chrom, start)-sorted index from the summed counts, as fslr_set_reads makes them
+  std::vector<int64_t> counts(c->chrom_counts);
+  counts.resize(static_cast<size_t>(r->n_chroms), 0);
+  std::vector<int2> cr(counts.size(), make_int2(0, 0));
+  int64_t acc = 0;
+  for (size_t ch = 0; ch < counts.size(); ++ch) {
+    counts[ch] += batch_counts[ch];
+    cr[ch] = make_int2(static_cast<int>(acc), static_cast<int>(acc + counts[ch]));
+    acc += counts[ch];
+  }
+  APP_TRY(c, hipMemcpyAsync(c->crange, cr.data(), cr.size() * sizeof(int2), hipMemcpyHostToDevice, st));
+  APP_TRY(c, hipStreamSynchronize(st));
+  std::swap(c->dchrom, w->alt_ch);
+  std::swap(c->drec, w->alt_rec);
+  std::swap(c->dgate, w->alt_gate);
+  w->alt_cap = old_cap_ni;                       // what the context's buffers were allocated for, at least
+  c->aln_zero_host.resize(static_cast<size_t>(need_ni), 0);
+  for (int64_t k = 0; k < mi; ++k) c->aln_zero_host[static_cast<size_t>(ni + k)] = r->iv_thr[k] == FSLR_THR_ZERO_ALN;
+  c->n = need_n;
+  c->ni = need_ni;
+  c->ni_idx = need_ni;
+  c->chrom_counts.swap(counts);
+  c->n_chroms = r->n_chroms;
+  c->thr_mode |= tmode;
+  c->any_zero_aln = c->any_zero_aln || any_zero;
+  ++c->reads_gen;
+  c->pf_set = c->pf_on = false;
+  c->edges_global = false;
+  c->cap_gmode = false;
+  ++c->input_gen;
+  if (prof) {
+    for (int t = 0; t < 2; ++t) HIP_TRY(c, hipEventElapsedTime(&w->ms[t], w->ev[t], w->ev[t + 1]));
+    HIP_TRY(c, hipEventElapsedTime(&w->ms[2], w->ev[3], w->ev[4]));
+    HIP_TRY(c, hipEventElapsedTime(&w->ms[3], w->ev[0], w->ev[4]));
+    w->timed = true;
+  }
+  return FSLR_OK;
+}
+
+int fslr_append_timings(fslr_ctx* c, float* ms) {
+  if (!c || !ms) return FSLR_ERR_INVALID;
+  AppendWork* w = c->apw;
+  if (!w || !w->timed)
+    return fail(c, FSLR_ERR_STATE, "fslr_append_timings: no profiled fslr_append_reads (fslr_set_profiling 1 or 2)");
+  for (int t = 0; t < 4; ++t) ms[t] = w->ms[t];
+  return FSLR_OK;
+}
+
+}  // extern "C"

@@ -6,6 +6,7 @@
 #include <cstring>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "fslr_hip.h"
@@ -18,42 +19,51 @@ namespace {
 
 int alloc_errw(fslr_ctx* c, int cap);
 
-int ensure_capacity(fslr_ctx* c, int64_t n, int64_t ni, int n_chroms) {
+// The buffers sized by the read, interval and chromosome counts.  `al(&ptr, count, keep)` (re)allocates one:
+// keep = how many elements hold resident reads (fslr_append_reads keeps them; fslr_set_reads does not).
+// data_order: dchrom / drec / dgate too (the append swaps merged ones of the new capacity in instead).
+template <class A>
+int size_buffers(fslr_ctx* c, int64_t n, int64_t ni, int n_chroms, bool data_order, A&& al) {
   int rc;
+  const size_t kn = static_cast<size_t>(c->n), kni = static_cast<size_t>(c->ni);
   if (n > c->cap_n) {
-    if ((rc = dalloc(c, &c->rmeta, n)) || (rc = dalloc(c, &c->rlen8, n)) || (rc = dalloc(c, &c->fwd, n)) ||
-        (rc = dalloc(c, &c->parent, n)) || (rc = dalloc(c, &c->forest, n)) ||
-        (rc = dalloc(c, &c->heavy, n)) ||
-        (rc = dalloc(c, &c->lbounds, n)))
+    if ((rc = al(&c->rmeta, n, kn)) || (rc = al(&c->rlen8, n, kn)) || (rc = al(&c->fwd, n, 0)) ||
+        (rc = al(&c->parent, n, 0)) || (rc = al(&c->forest, n, 0)) ||
+        (rc = al(&c->heavy, n, 0)) ||
+        (rc = al(&c->lbounds, n, 0)))
       return rc;
 #ifdef FSLR_SECTION_PROF
-    if ((rc = dalloc(c, &c->diag, 2 * n))) return rc;
+    if ((rc = al(&c->diag, 2 * n, 0))) return rc;
 #endif
     c->cap_n = n;
   }
   if (ni > c->cap_ni) {
-    if ((rc = dalloc(c, &c->iv, ni)) || (rc = dalloc(c, &c->qpos, ni)) || (rc = dalloc(c, &c->rng_s, ni)) || (rc = dalloc(c, &c->swin, ni)) || (rc = dalloc(c, &c->idx4, ni)) ||
-        (rc = dalloc(c, &c->idx_gate, ni)) || (rc = dalloc(c, &c->data_pos, ni)) ||
-        (rc = dalloc(c, &c->dchrom, ni)) || (rc = dalloc(c, &c->drec, ni)) || (rc = dalloc(c, &c->dgate, ni)) ||
-        (rc = dalloc(c, &c->chist, (ni / 1024 + 1) * 64)) || (rc = dalloc(c, &c->s_start, ni)) ||
-        (rc = dalloc(c, &c->keys, ni)) || (rc = dalloc(c, &c->keys2, ni)) || (rc = dalloc(c, &c->vals, ni)) ||
-        (rc = dalloc(c, &c->vals2, ni)) || (rc = dalloc(c, &c->endkey, ni)) || (rc = dalloc(c, &c->pmaxkey, 2 * (ni / 256) + ni / (256 * 1024) + 8)) ||
-        (rc = dalloc(c, &c->thr_tmp, ni)))
+    if ((rc = al(&c->iv, ni, kni)) || (rc = al(&c->qpos, ni, 0)) || (rc = al(&c->rng_s, ni, 0)) || (rc = al(&c->swin, ni, 0)) || (rc = al(&c->idx4, ni, 0)) ||
+        (rc = al(&c->idx_gate, ni, 0)) || (rc = al(&c->data_pos, ni, kni)) ||
+        (data_order && ((rc = al(&c->dchrom, ni, 0)) || (rc = al(&c->drec, ni, 0)) || (rc = al(&c->dgate, ni, 0)))) ||
+        (rc = al(&c->chist, (ni / 1024 + 1) * 64, 0)) || (rc = al(&c->s_start, ni, 0)) ||
+        (rc = al(&c->keys, ni, 0)) || (rc = al(&c->keys2, ni, 0)) || (rc = al(&c->vals, ni, 0)) ||
+        (rc = al(&c->vals2, ni, 0)) || (rc = al(&c->endkey, ni, 0)) || (rc = al(&c->pmaxkey, 2 * (ni / 256) + ni / (256 * 1024) + 8, 0)) ||
+        (rc = al(&c->thr_tmp, ni, 0)))
       return rc;
     c->cap_ni = ni;
     size_t need = 0;
     HIP_TRY(c, index_temp_bytes(static_cast<int>(ni), &need, c->stream));
     if (need > c->temp_bytes) {
-      if (c->temp) (void)hipFree(c->temp);
-      c->temp = nullptr;
-      HIP_TRY(c, hipMalloc(&c->temp, need));
+      if ((rc = al(reinterpret_cast<unsigned char**>(&c->temp), need, 0))) return rc;
       c->temp_bytes = need;
     }
   }
   if (n_chroms > c->cap_chroms) {
-    if ((rc = dalloc(c, &c->crange, n_chroms))) return rc;
+    if ((rc = al(&c->crange, n_chroms, 0))) return rc;
     c->cap_chroms = n_chroms;
   }
+  return FSLR_OK;
+}
+
+int ensure_capacity(fslr_ctx* c, int64_t n, int64_t ni, int n_chroms) {
+  int rc = size_buffers(c, n, ni, n_chroms, true, [c](auto** p, size_t count, size_t) { return dalloc(c, p, count); });
+  if (rc) return rc;
   if (!c->umax) {
     if ((rc = dalloc(c, &c->umax, FSLR_MAX_L))) return rc;
     if ((rc = dalloc(c, &c->counters, kNumCounters))) return rc;
@@ -130,6 +140,44 @@ int thr_mode_of(const int32_t* thr, int64_t ni) {
 
 }  // namespace
 
+// Every buffer that has to grow is allocated before any is freed: when memory runs out the new ones are
+// released and the context (its reads, its index) is as it was.  Then the resident contents are copied on
+// the stream and the old buffers freed.
+int fslr::grow_capacity_keep(fslr_ctx* c, int64_t n, int64_t ni, int n_chroms) {
+  struct Staged {
+    void** slot;
+    void* fresh;
+    size_t keep_bytes;
+  };
+  std::vector<Staged> st;
+  const int64_t cap_n = c->cap_n, cap_ni = c->cap_ni, cap_chroms = c->cap_chroms;
+  const size_t temp_bytes = c->temp_bytes;
+  int rc = size_buffers(c, n, ni, n_chroms, false, [&](auto** p, size_t count, size_t keep) {
+    using T = std::remove_pointer_t<std::remove_pointer_t<decltype(p)>>;
+    void* q = nullptr;
+    const hipError_t e = hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T));
+    if (e != hipSuccess) return fail(c, FSLR_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    st.push_back({reinterpret_cast<void**>(p), q, *p ? keep * sizeof(T) : 0});
+    return static_cast<int>(FSLR_OK);
+  });
+  hipError_t e = hipSuccess;
+  if (!rc)
+    for (const Staged& s : st)
+      if (s.keep_bytes && e == hipSuccess)
+        e = hipMemcpyAsync(s.fresh, *s.slot, s.keep_bytes, hipMemcpyDeviceToDevice, c->stream);
+  if (!rc && e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (rc || e != hipSuccess) {
+    for (const Staged& s : st) (void)hipFree(s.fresh);
+    c->cap_n = cap_n, c->cap_ni = cap_ni, c->cap_chroms = cap_chroms, c->temp_bytes = temp_bytes;
+    return rc ? rc : fail(c, FSLR_ERR_HIP, std::string("grow_capacity_keep copy: ") + hipGetErrorString(e));
+  }
+  for (const Staged& s : st) {
+    if (*s.slot) (void)hipFree(*s.slot);
+    *s.slot = s.fresh;
+  }
+  return FSLR_OK;
+}
+
 extern "C" {
 
 int fslr_abi_version(void) { return FSLR_ABI_VERSION; }
@@ -182,6 +230,7 @@ void fslr_ctx_destroy(fslr_ctx* c) {
   fslr_coverage_free(c);
   fslr_cluster_free(c);
   fslr_match_free(c);
+  fslr_append_free(c);
   if (c->ev_ok) {
     for (auto& e : c->ev) (void)hipEventDestroy(e);
     for (auto& e : c->kev) (void)hipEventDestroy(e);

@@ -180,6 +180,7 @@ struct fslr_ctx {
   uint64_t index_gen = 0;                // bumped by every fslr_build_index (a saved search batch belongs to one)
   struct ScoreWork* scw = nullptr;       // fslr_score_pairs' scratch and its last call's times (score.hip)
   struct CoverageWork* cvw = nullptr;    // fslr_coverage_build's resident keys, the chunk staging (coverage.hip)
+  struct AppendWork* apw = nullptr;      // fslr_append_reads' batch scratch and the second set of data-order buffers (append.hip)
   struct MatchWork* mtw = nullptr;       // fslr_match_reads' block and chunk scratch, its last batch's rows (match.hip)
   struct ClusterWork* clw = nullptr;     // fslr_cluster_table's resident table, the assign / representatives scratch (clusters.hip)
   // reads of more than FSLR_MAX_L intervals (long.hip): the virtual-read map and the long-pair stage
@@ -238,11 +239,19 @@ void fslr_coverage_free(fslr_ctx* c);
 void fslr_cluster_free(fslr_ctx* c);
 // frees the read matching's buffers and its saved batch (match.hip)
 void fslr_match_free(fslr_ctx* c);
+// frees the append's batch scratch and its second set of data-order buffers (append.hip)
+void fslr_append_free(fslr_ctx* c);
 
 namespace fslr {
 
 // builds the walk engine's index parts of a sweep-only index (capi.hip); no-op when present
 int ensure_walk_index(fslr_ctx* c);
+// ensure_capacity for fslr_append_reads (capi.hip): the buffers that hold the resident reads (rmeta, rlen8, iv,
+// data_pos) grow with their contents kept; dchrom / drec / dgate are left to the caller, which swaps merged
+// buffers of at least the new capacity in; everything else is scratch or index data and is re-allocated.
+// All of it is allocated before anything is freed: FSLR_ERR_NOMEM leaves the context, its index included,
+// as it was (a grown buffer set replaces index data: the caller rebuilds the index afterwards)
+int grow_capacity_keep(fslr_ctx* c, int64_t n, int64_t ni, int n_chroms);
 // {edge count, error code, max forward degree} of the last query through pinned memory; syncs
 int peek_counts(fslr_ctx* c, long long out[4]);   // edges, err code, max_fwd, ZeroDivisionError pairs
 // the backward scan ranges of the (possibly chromosome-filtered) index, without the CSR map (capi.hip)

@@ -287,6 +287,9 @@ struct UploadArgs {
   const int *off, *qlen2, *nal, *chrom, *start, *end, *thr, *dp;   // dp null: no data order
   int n, ni, n_chroms;
   bool reads_ok;                      // read_off passed the host checks (k_up_reads / k_up_data may run)
+  // fslr_append_reads packs a batch behind the resident reads: its read r has rank rank_base + r and its
+  // intervals follow at CSR offset off_base (0, 0: fslr_set_reads)
+  int rank_base = 0, off_base = 0;
   // outputs
   int4* iv;
   int4* rmeta;

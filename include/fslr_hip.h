@@ -69,6 +69,9 @@
  *   fslr_match_rows       cluster.py:197-222 the pair loop for query reads that are not in the uploaded set:
  *                         the search (:201), the seen-set (:205-208) and the pair predicates (:209-219)
  *                         against the resident index, without the edge cap (:223-224)
+ *   fslr_append_reads     cluster.py:109-121, 189-191 prepare_data's start-sorted `data` list and the per-read
+ *                         lists for a set that grows: the lists of the union, made from the resident ones and
+ *                         a new batch's (the reference rebuilds both from the whole frame)
  *
  * Conventions: plain C types, caller-owned host arrays, library-owned device
  * memory behind an opaque context.  Every function returns FSLR_OK (0) or an
@@ -720,8 +723,8 @@ int  fslr_cluster_timings(fslr_ctx *ctx, float *ms);
  * FSLR_MATCH_SET: the distinct partners of one query read held in on-chip memory; a read with more is
  * still exact (its later hits are deduplicated against the staged hit list) but slower.
  * Out of scope: the edge cap (:223-224; a matched read's loop is not part of the resident graph's cap
- * replay, so every candidate is evaluated), matching through the multi-GPU split, and inserting matched
- * reads into the index.  Query or resident reads of more than FSLR_MAX_L intervals: fslr_match_reads_any.
+ * replay, so every candidate is evaluated) and matching through the multi-GPU split.  Matched reads join
+ * the resident set through fslr_append_reads (below).  Query or resident reads of more than FSLR_MAX_L intervals: fslr_match_reads_any.
  * fslr_match_timings (fslr_set_profiling 1 or 2): HIP-event times (ms) of the last fslr_match_reads,
  * ms[0..3] = upload, search (count + fill), dedupe + score (+ row compaction), download, summed over its
  * blocks and chunks. */
@@ -782,6 +785,44 @@ int  fslr_match_reads_any(fslr_ctx *ctx, const fslr_params *params, const int32_
                           const fslr_match_queries *queries, uint32_t emit_mask, int64_t *row_off, int32_t *counts,
                           int32_t *best, int64_t *n_rows);
 int  fslr_match_rows_any(fslr_ctx *ctx, int32_t *partner, int32_t *I, int32_t *U, uint8_t *flags, int64_t capacity);
+
+/* Append reads to the resident set on the device: what a caller otherwise does by
+ * fslr_set_reads of the union.  `reads` describes m new reads with mi intervals exactly as fslr_set_reads
+ * takes them: iv_chrom in the resident dense ids, n_chroms >= the resident n_chroms (a larger value adds
+ * chromosomes at the end), folded iv_thr, and iv_data_pos REQUIRED: the position of each new interval in the
+ * batch's own start-sorted list (a permutation of [0, mi) with non-decreasing starts).
+ * After a successful call the context holds n + m reads: the resident reads keep ranks 0 .. n-1 and their CSR
+ * rows, new read r has rank n + r and its intervals follow at CSR offset ni + read_off[r].  The `data` list is
+ * the stable merge of the two start-sorted lists, the resident element first on equal starts: a resident
+ * interval at data position d with start s moves to d + #{new intervals with start < s}, a new interval at
+ * its own position e with start t lands at e + #{resident intervals with start <= t}.  Every resident buffer
+ * and host-side count then equals, byte for byte, what fslr_set_reads gives for the concatenated CSR with
+ * that merged iv_data_pos; the same bytes on every run.  As after fslr_set_reads: no index is built
+ * (fslr_build_index next), the saved search, match and score batches, the position plan and the query-reuse
+ * state belong to the old reads.  Thresholds are the resident ones currently set plus the batch's.
+ * Cost: H2D of the m-sized columns only, no D2H of resident columns and no host pass over resident reads;
+ * device buffers that must grow keep their contents.  Syncs.
+ * Atomic: the whole batch is validated before any resident buffer is written.  The first failure is reported
+ * as fslr_set_reads reports it (FSLR_ERR_INVALID, the same messages; also n + m >= FSLR_MAX_READS, ni + mi >=
+ * 2^31 - 1, a NULL iv_data_pos, n_chroms below the resident value) and leaves the context as it was: the same
+ * reads, the index still built if it was, the saved batches readable.  m == 0 is valid and changes nothing.
+ * Memory is part of that: every buffer that has to grow and the merge output are allocated before anything
+ * is freed or written, so FSLR_ERR_NOMEM leaves the context as it was too.  Only a device failure after that
+ * point (FSLR_ERR_HIP from a copy or a launch) leaves no reads set.
+ * Memory: from the first append on the context keeps a second set of data-order buffers (28 B per interval
+ * of capacity, the merge writes into it and the sets swap) and the batch scratch (about 85 B per interval
+ * of the largest batch) until fslr_ctx_destroy; growth allocates the new buffers beside the old ones, so
+ * its peak is both.
+ * FSLR_ERR_STATE, named in the message: no reads set; reads set without iv_data_pos; reads made from rows
+ * (fslr_set_reads_rows); virtual reads (fslr_set_reads_any with a long read, fslr_set_long_reads); n_shards >
+ * 1; a chromosome or position filter active.  A new read of more than FSLR_MAX_L intervals is
+ * FSLR_ERR_INVALID.  Multi-GPU contexts do not append.
+ * FSLR_APPEND_TILE: outputs per tile of the merge kernel (a block finds each tile's split by binary search).
+ * fslr_append_timings (fslr_set_profiling 1 or 2): HIP-event times (ms) of the last fslr_append_reads,
+ * ms[0..3] = upload, validate + pack, merge (row copies, merge, data positions), first to last event. */
+#define FSLR_APPEND_TILE 1024
+int  fslr_append_reads(fslr_ctx *ctx, const fslr_reads *reads);
+int  fslr_append_timings(fslr_ctx *ctx, float *ms);
 
 /* Device-side views for collectives (e.g. RCCL all_gather of labels). */
 int  fslr_labels_device_ptr(fslr_ctx *ctx, void **dptr);
