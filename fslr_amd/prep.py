@@ -280,6 +280,44 @@ def build_csr(data: IntervalData) -> CSR:
                start_sorted=bool(n_iv < 2 or np.all(np.diff(np.asarray(data.start, np.int64)) >= 0)))
 
 
+def kept_data_rows(csr: CSR, keep) -> np.ndarray:
+    """Per position of the `data` list the CSR was built from: does its element belong to a read with
+    ``keep[rank]`` true.  ``data.select(kept_data_rows(csr, keep))`` is the list without the other reads."""
+    keep = np.asarray(keep, dtype=bool)
+    if keep.shape != (csr.n_reads,):
+        raise ValueError(f'keep needs one entry per read ({csr.n_reads}), got shape {keep.shape}')
+    rows = np.empty(csr.n_intervals, dtype=bool)
+    rows[np.asarray(csr.data_pos, np.int64)] = np.repeat(keep, np.diff(np.asarray(csr.read_off, np.int64)))
+    return rows
+
+
+def remove_reads_csr(csr: CSR, keep):
+    """The CSR without the reads whose ``keep`` entry (over the read ranks) is false, and the old rank ->
+    new rank map (int32, -1 for a removed read): what the reference's delete_false (cluster.py:80-86)
+    followed by prepare_data (:109-121, :189-191) gives for the frame without those reads.  The survivors'
+    `data` list is a subsequence of the old one, so their first-appearance ranks are the old ranks with the
+    gaps closed, their intervals keep their order at the closed-up CSR offsets, and an interval at data
+    position d moves to #{kept elements before d}: ``build_csr(data.select(kept_data_rows(csr, keep)))``
+    column for column, except that ``n_chroms`` and the dense chromosome ids stay as they are (a chromosome
+    may be left without intervals), so ids handed out earlier remain valid.  O(n) numpy selections; no sort.
+    Keeping nothing raises ValueError."""
+    keep = np.asarray(keep, dtype=bool)
+    rows = kept_data_rows(csr, keep)
+    if not keep.any():
+        raise ValueError('remove_reads_csr would leave no reads')
+    lens = np.diff(np.asarray(csr.read_off, np.int64))
+    keep_iv = np.repeat(keep, lens)
+    newpos = np.cumsum(rows) - rows                       # kept elements before each data position
+    off = np.zeros(int(keep.sum()) + 1, dtype=np.int64)
+    np.cumsum(lens[keep], out=off[1:])
+    out = CSR(read_off=off.astype(np.int32), read_qlen2=csr.read_qlen2[keep], read_nal=csr.read_nal[keep],
+              iv_chrom=csr.iv_chrom[keep_iv], iv_start=csr.iv_start[keep_iv], iv_end=csr.iv_end[keep_iv],
+              iv_aln=csr.iv_aln[keep_iv], n_chroms=csr.n_chroms, read_qcode=np.asarray(csr.read_qcode)[keep],
+              data_pos=newpos[np.asarray(csr.data_pos, np.int64)[keep_iv]], nal_varies=csr.nal_varies,
+              start_sorted=csr.start_sorted)
+    return out, np.where(keep, np.cumsum(keep) - 1, -1).astype(np.int32)
+
+
 def has_long_reads(csr: CSR) -> bool:
     return bool(csr.n_reads and np.diff(csr.read_off).max() > FSLR_MAX_L)
 
