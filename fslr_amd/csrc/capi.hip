@@ -1867,6 +1867,7 @@ int fslr_union_pairs(fslr_ctx* c, const int32_t* src, const int32_t* dst, int64_
   c->hooked = false;
   HIP_TRY(c, hipSetDevice(c->device));
   if (n == 0) return FSLR_OK;
+  if (!src && !c->n) return fail(c, FSLR_ERR_INVALID, "no reads");   // before the temporary below
   const int* ds = src;
   const int* dd = dst;
   int* tmp = nullptr;
@@ -1879,7 +1880,6 @@ int fslr_union_pairs(fslr_ctx* c, const int32_t* src, const int32_t* dst, int64_
       ds = tmp + n;
     }
   }
-  if (!src && !c->n) return fail(c, FSLR_ERR_INVALID, "no reads");
   HIP_TRY(c, launch_uf_pairs(c->parent, ds, dd, n, static_cast<int>(c->n), c->stream));
   if (tmp) {
     HIP_TRY(c, hipFreeAsync(tmp, c->stream));

@@ -97,12 +97,13 @@ __global__ void k_uf_hook_min_pairs(int* p, const int2* __restrict__ pairs, long
   }
 }
 
-// a gathered edge list (the multi-GPU merge): (a, b) pairs, a < 0 = padding
+// a gathered edge list (the multi-GPU merge): (a, b) pairs, a < 0 or b < 0 = padding, as the pre-hook
+// above takes it (a row with only b < 0 would otherwise walk from p[-1])
 __global__ void k_uf_pair_list(int* p, const int2* __restrict__ pairs, long long n) {
   for (long long k = blockIdx.x * static_cast<long long>(blockDim.x) + threadIdx.x; k < n;
        k += static_cast<long long>(gridDim.x) * blockDim.x) {
     const int2 e = pairs[k];
-    if (e.x >= 0) uf_union(p, e.x, e.y);
+    if (e.x >= 0 && e.y >= 0) uf_union(p, e.x, e.y);
   }
 }
 

@@ -832,8 +832,9 @@ int  fslr_copy_labels_device(fslr_ctx *ctx, int32_t *dst);
 int  fslr_copy_fwd_device(fslr_ctx *ctx, int32_t *dst);
 /* Union (src[k], dst[k]) into the context's forest; pointers are device pointers
  * on this context's device when on_device != 0, else host.  src == NULL means
- * src[k] = k mod n_reads, so W concatenated label vectors merge in one call.
- * Follow with fslr_finalize_labels.  Async. */
+ * src[k] = k mod n_reads, so W concatenated label vectors merge in one call
+ * (FSLR_ERR_INVALID on a context without reads).  There is no padding: every
+ * end must lie in [0, n_reads).  Follow with fslr_finalize_labels.  Async. */
 int  fslr_union_pairs(fslr_ctx *ctx, const int32_t *src, const int32_t *dst, int64_t n, int on_device);
 int  fslr_finalize_labels(fslr_ctx *ctx);
 /* Copy this context's edges as int32 (a, b) pairs into a caller-owned device buffer of n_pad pairs,
@@ -841,7 +842,8 @@ int  fslr_finalize_labels(fslr_ctx *ctx);
  * (the multi-GPU merge pads every rank to the largest count).  Async, ctx stream. */
 int  fslr_copy_edges_device(fslr_ctx *ctx, int32_t *dst, int64_t n_pad);
 /* Labels = connected components (min-rank roots) of the n int32 (a, b) device pairs at `pairs`
- * (pairs with a < 0 are skipped): the union of W ranks' gathered edge lists.  Async. */
+ * (a pair with a < 0 or b < 0 is padding and is skipped, by the pre-hook and by the union alike; every
+ * other end must lie in [0, n_reads)): the union of W ranks' gathered edge lists.  Async. */
 int  fslr_components_from_pairs(fslr_ctx *ctx, const int32_t *pairs, int64_t n);
 
 #ifdef __cplusplus

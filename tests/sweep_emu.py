@@ -252,14 +252,15 @@ class EmuSweepContext:
 
     def forest_pairs_into(self, t, n_pad):
         pairs = np.full((n_pad, 2), -1, dtype=np.int32)
-        pairs[:len(self._forest)] = self._forest
+        f = self._forest[:n_pad]
+        pairs[:len(f)] = f
         t.numpy()[:n_pad] = pairs.view(np.int64)[:, 0]
 
     def components_from_pairs(self, t, n):
         pairs = t.numpy()[:n].view(np.int32).reshape(-1, 2)
         self._parent = np.arange(self.n_reads)
         for x, y in pairs.tolist():
-            if x >= 0:
+            if x >= 0 and y >= 0:
                 self._union(x, y)
 
     def union_label_vectors(self, t):
@@ -374,8 +375,9 @@ class EmuSweepContext:
 
     # -- the sharded edge cap (fslr_cap_install_pairs ... fslr_cap_apply_changes) ------------------
     def sort_edges(self):
+        """fslr_sort_edges: grouped by a, each run in its previous order (a stable sort by a alone)."""
         if len(self._edges):
-            self._edges = self._edges[np.lexsort((self._edges[:, 1], self._edges[:, 0]))]
+            self._edges = self._edges[np.argsort(self._edges[:, 0], kind='stable')]
 
     def cap_bwd_counts(self, edge_threshold, t):
         import torch
