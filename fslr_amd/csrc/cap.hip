@@ -2012,8 +2012,9 @@ void set_space(fslr_ctx* c, CapWork* w) {
 // The closure over an edge list: rounds over every edge and read (default), or FSLR_CAP_CLOSURE=frontier,
 // rounds over the joined reads' forward edges only, through an adjacency built with per-edge atomics.
 // Measured at cfg5 (profiles/r04/r4e/): the whole replay 5.15 ms with rounds, 5.9 ms with the frontier
-// (its adjacency build, 1.2 ms, costs more than the rounds it saves).  Gathered rows sorted by lower
-// read (the sharded replay) have their adjacency for free and always take the frontier.
+// (its adjacency build, 1.2 ms, costs more than the rounds it saves).  Rows that are one run per lower
+// read (the sharded replay's sorted gather, the sweep engine's edge list on one GPU) have their
+// adjacency for free and always take the frontier; unsorted gathered rows are an edge list like any other.
 bool cap_rounds_closure() {
   static const bool v = [] {
     const char* e = std::getenv("FSLR_CAP_CLOSURE");
@@ -2136,7 +2137,8 @@ int cap_local(fslr_ctx* c, int thr, CapWork* w, const int2* E, const int* F, int
   }
   HIP_TRY(c, hipMemsetAsync(w->err, 0, 4 * sizeof(int), s));
   HIP_TRY(c, hipMemsetAsync(w->stats, 0, kStWords * sizeof(long long), s));
-  // 1. closure.  Frontier rounds (batches of 16, one sync per batch), or FSLR_CAP_CLOSURE=rounds:
+  // 1. closure.  Rows that come as one run per read (rstart / rend), or FSLR_CAP_CLOSURE=frontier: frontier
+  // rounds (batches of 16, one sync per batch).  Otherwise (the default for an edge list without runs):
   // rounds over every edge and read in batches of 8 (chg[0] = 1 starts each batch)
   const bool frontier = !all_reads && (rstart || !cap_rounds_closure());
   if (all_reads) k_cap_all<<<grid_for(n), 256, 0, s>>>(w->state, static_cast<int>(n), w->all_shard, w->all_n_shards);
@@ -2591,7 +2593,14 @@ extern "C" int fslr_apply_edge_cap(fslr_ctx* c, int32_t thr, fslr_cap_stats* out
   bool binds = false;
   if (int rc = cap_peek(c, thr, &ne, &binds)) return rc;
   if (!binds) {
-    if (out) *out = c->cap_stats;
+    if (out) {
+      // a call on a graph this query's replay has already capped replays nothing: applied = 0, the
+      // capped graph's max_fwd (post-break walks can leave it above the threshold)
+      const bool again = c->cap_stats.applied != 0;
+      if (again) std::memset(out, 0, sizeof(*out));
+      else *out = c->cap_stats;
+      if (again) out->max_fwd = c->cap_stats.max_fwd;
+    }
     return FSLR_OK;
   }
   if (!c->last_full && !c->edges_global)
@@ -2940,7 +2949,7 @@ int cap_install(fslr_ctx* c, const int32_t* pairs, int64_t n_rows, int32_t world
   HIP_TRY(c, hipStreamSynchronize(s));
   w->g_sorted = !flag && tot[0] == tot[1];
   if (cap_debug()) std::fprintf(stderr, "fslr: cap install %lld rows, sorted %d\n", static_cast<long long>(n_rows), w->g_sorted);
-  if (!w->g_sorted) {                 // unsorted blocks: forward degrees by atomics, the closure by adjacency
+  if (!w->g_sorted) {                 // unsorted blocks: forward degrees by atomics, the closure as for an edge list
     HIP_TRY(c, hipMemsetAsync(w->gfwd, 0, nb, s));
     if (n_rows) k_cap_gfwd<<<grid_for(n_rows), 256, 0, s>>>(w->grows, n_rows, w->gfwd);
     HIP_TRY(c, hipGetLastError());

@@ -311,7 +311,12 @@ int  fslr_query_shard(fslr_ctx *ctx, const fslr_params *params, int32_t shard, i
  * counter read) when the cap does not bind.  Needs the last query to be fslr_query over all reads
  * (or fslr_cap_install_edges on an unfiltered index).  The replay runs on the device: loops of
  * different components of the candidates' partner graph are independent.
- * Call between fslr_query and fslr_components.  Syncs; out may be NULL. */
+ * Call between fslr_query and fslr_components.  Syncs; out may be NULL.
+ * edge_threshold <= 0 is replayed like any other value: the reference's check `edges >= edge_threshold`
+ * (:223) then holds from the start, so every read is a candidate (reads without hits too) and every
+ * interval's visit ends at its first new pair that passes the gate with I > 0, edge or not.
+ * A second call after a replay, without a new query, leaves the capped graph alone and reports
+ * applied = 0 with the capped graph's max_fwd (which post-break walks can leave above the threshold). */
 int  fslr_apply_edge_cap(fslr_ctx *ctx, int32_t edge_threshold, fslr_cap_stats *out);
 /* The same check without a host round trip, for a repeated query on unchanged input: the device ORs
  * (max forward degree > edge_threshold) | (a listed ZeroDivisionError pair) << 1 into a sticky word (async);
@@ -438,7 +443,8 @@ int  fslr_local_forest(fslr_ctx *ctx, int64_t *n_pairs);
 int  fslr_copy_forest_pairs(fslr_ctx *ctx, int32_t *dst, int64_t n_pad);
 /* fslr_sort_edges: this context's edge list (with I, U) grouped by a, stably, in place (syncs once for
  * the count).  The sharded cap's ranks sort before the gather, so each read's forward edges are one run of
- * the gathered rows (the closure walks the runs; unsorted blocks still work, through an adjacency). */
+ * the gathered rows (the closure walks the runs; unsorted blocks still work: their closure runs over
+ * every row per round, as for a context's own edge list). */
 int  fslr_sort_edges(fslr_ctx *ctx);
 int  fslr_cap_install_pairs(fslr_ctx *ctx, const int32_t *pairs, int64_t n_rows, int32_t world, int32_t rank);
 int  fslr_cap_sizes(fslr_ctx *ctx, int64_t *n_t, int64_t *n_ti, int64_t *n_hits);
