@@ -1,11 +1,15 @@
-// firstfit.hpp — the pair predicates of an ordered pair (list1, list2) as score.hip and match.hip
-// evaluate them: the length gate's flags, the lane-group first-fit of overall_jaccard_similarity
-// (cluster.py:140-170) and the packed result word I | U << 8 | flags << 16.  thr_ok, iv_match_general
-// and lengths_pass are those of kernels.hpp.
+// firstfit.hpp — the pair predicates of an ordered pair (list1, list2): the length gate's flags, the
+// first-fit of overall_jaccard_similarity (cluster.py:140-170) and the packed result word
+// I | U << 8 | flags << 16.  thr_ok, iv_match_general and lengths_pass are those of kernels.hpp.  This
+// is the one place on the device that states the greedy; its users:
+//   score.hip  k_score_pairs<kAny>: FirstFit::row on 16-, 32- and 64-lane groups, long_fit for long pairs
+//   match.hip  k_match_score<kAny>: the same, list1's rows read from LDS
+//   cap.hip    k_cap_eval: lane_fit for two short reads, long_fit for every other slot
+//   query.hip  deferred_kernel: FirstFit::row<64> for a deferred pair
 //
 // List2's columns sit on the lanes of a W-lane group (W in {16, 32, 64}; 64 / W pairs side by side in a
 // wavefront), list1's rows are stepped uniformly over the group: where a row comes from (a broadcast
-// record in score.hip, LDS in match.hip) is the caller's.
+// record in score.hip and query.hip, LDS in match.hip) is the caller's.
 #pragma once
 #include <cstdint>
 
@@ -62,6 +66,37 @@ struct FirstFit {
     used = u, zd = z, I = n;
   }
 };
+
+// The scalar statement of the same rule, by one lane, for two reads of few intervals (LB <= 32: one bit of
+// `used` per column; cap.hip takes it up to 16): rows ascending, the lowest unused column of the row's
+// chromosome that matches or, where either interval has aln_size == 0, raises.  FirstFit::row is this loop
+// with the columns on lanes: cand = column unused and same chromosome, zero = the raise, hit = zero or
+// match, and the row takes the lowest hit.
+__device__ __forceinline__ void lane_fit(const int4* __restrict__ iv, int oa, int ob, int LA, int LB, int* I_out,
+                                         bool* zd_out) {
+  unsigned used = 0u;
+  int I = 0;
+  bool zd = false;
+  for (int i = 0; i < LA && !zd; ++i) {
+    const int4 ai = iv[oa + i];
+    for (int j = 0; j < LB; ++j) {
+      if ((used >> j) & 1u) continue;
+      const int4 bj = iv[ob + j];
+      if (bj.x != ai.x) continue;
+      if (ai.w == FSLR_THR_ZERO_ALN || bj.w == FSLR_THR_ZERO_ALN) {
+        zd = true;
+        break;
+      }
+      if (iv_match_general(ai.y, ai.z, ai.w, bj.y, bj.z, bj.w)) {
+        used |= 1u << j;
+        ++I;
+        break;
+      }
+    }
+  }
+  *I_out = I;
+  *zd_out = zd;
+}
 
 // the result word of a pair of LA x LB intervals with I matches: I | U << 8 | flags << 16 (pt: the pass
 // table); calculate_overlap's ZeroDivisionError ends the pair with I = U = 0

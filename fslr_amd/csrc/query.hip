@@ -28,6 +28,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "firstfit.hpp"
 #include "kernels.hpp"
 #include "wave.hpp"
 
@@ -698,7 +699,6 @@ __global__ __launch_bounds__(256) void deferred_kernel(QueryArgs g) {
     const unsigned kind = static_cast<unsigned>(e & 3u);
     const int4 am = sload4(g.rmeta, a), bm = sload4(g.rmeta, B);
     const int LA = am.y & 0xffff, LB = bm.y & 0xffff;
-    const bool haz = ((am.y | bm.y) >> 16) & 1;
     int4 ai = make_int4(-1, 0, 0, 0), bj = make_int4(-2, 0, 0, 0);
     if (lane < LA) ai = g.iv[am.x + lane];
     if (lane < LB) bj = g.iv[bm.x + lane];
@@ -727,19 +727,14 @@ __global__ __launch_bounds__(256) void deferred_kernel(QueryArgs g) {
     int I = 0;
     if (work) {
       ++w_gather;
-      bool used = false;
-      for (int i = 0; i < LA; ++i) {
-        const int c = rdl(ai.x, i), si = rdl(ai.y, i), ei = rdl(ai.z, i), ti = rdl(ai.w, i);
-        const bool cand = lane < LB && !used && bj.x == c;
-        const bool zero = haz && cand && (ti == FSLR_THR_ZERO_ALN || bj.w == FSLR_THR_ZERO_ALN);
-        const bool hit = cand && (zero || iv_match_general(si, ei, ti, bj.y, bj.z, bj.w));
-        const unsigned long long hm = __ballot(hit);
-        if (!hm) continue;
-        const int j = __builtin_ctzll(hm);
-        if (__shfl(static_cast<int>(zero), j)) { zd = true; break; }
-        if (lane == j) used = true;
-        ++I;
-      }
+      // the shared first-fit on the whole wave (firstfit.hpp); rows after a ZeroDivisionError are no-ops.
+      // It tests the zero-aln sentinel on every pair: rmeta.y bit 16 of a read is set exactly when one of its
+      // intervals carries the sentinel (upload.hip), so gating the test on those bits would change nothing.
+      FirstFit ff;
+      for (int i = 0; i < LA && !ff.zd; ++i)
+        ff.row<kWave>(rdl(ai.x, i), rdl(ai.y, i), rdl(ai.z, i), rdl(ai.w, i), true, bj, lane < LB, lane);
+      I = ff.I;
+      zd = ff.zd;
       if (lane == 0) raise_zd(g.err, zd, a, B);
     }
     const int U = LA + LB - I;

@@ -24,7 +24,7 @@
 // 4 B out.
 //
 // fslr_score_pairs_any (reads of up to FSLR_MAX_ANY_L intervals): on a context without
-// virtual reads it is the driver and the kernel above.  On one with virtual reads k_score_pairs_any takes
+// virtual reads it is the driver and k_score_pairs<false>.  On one with virtual reads k_score_pairs<true> takes
 // real ranks: a read's list is its first chunk at rmeta[r].x and the rest from lg_off2[r], lg_rlen[r]
 // intervals in all.  A wave whose four pairs are all of two lists <= FSLR_MAX_L keeps the lane groups; a
 // wave that meets a longer pair runs its pairs one at a time on 64 lanes, the long ones through long_fit
@@ -82,17 +82,24 @@ struct ScoreArgs {
   const int* a;
   const int* b;
   unsigned* out;
-  int n_pairs, n_reads, ni;
+  int n_pairs, n_reads, ni;          // <true>: n_reads counts the real reads
   double qcut, ncut;
   int wide;                          // (timing tool) every pair on a full 64-lane group
+  // <true> kernel only: real ranks on a context with virtual reads
+  const int* rlen;                   // [n_real] a real read's interval count
+  const int* off2;                   // [n_real] where a long read's intervals beyond FSLR_MAX_L begin
+  const int* umax;
+  int n_umax;
 };
 
 struct PairMeta {
   int offA, LA, offB, LB, gate;      // gate: FSLR_SCORE_GATE or FSLR_SCORE_ZD_GATE or 0
+  int offA2, offB2;                  // <true>: offA, offB are the first chunks, LA, LB the real lengths
 };
 
+template <bool kAny>
 __device__ __forceinline__ PairMeta pair_meta(const ScoreArgs& s, int k, bool valid) {
-  PairMeta m{0, 0, 0, 0, 0};
+  PairMeta m{0, 0, 0, 0, 0, 0, 0};
   if (valid) {
     const int ra = s.a[k], rb = s.b[k];
     FSLR_BOUND(ra, s.n_reads);
@@ -103,6 +110,12 @@ __device__ __forceinline__ PairMeta pair_meta(const ScoreArgs& s, int k, bool va
     m.offB = mb.x;
     m.LB = mb.y & 0xffff;
     m.gate = gate_flags(ma.z, mb.z, ma.w, mb.w, s.qcut, s.ncut);
+    if constexpr (kAny) {
+      m.LA = s.rlen[ra];
+      m.LB = s.rlen[rb];
+      if (m.LA > FSLR_MAX_L) m.offA2 = s.off2[ra];
+      if (m.LB > FSLR_MAX_L) m.offB2 = s.off2[rb];
+    }
   }
   return m;
 }
@@ -146,12 +159,25 @@ __device__ __forceinline__ FirstFit group_fit(const ScoreArgs& s, bool valid, co
   return ff;
 }
 
-template <int W>
-__device__ __forceinline__ void score_groups(const ScoreArgs& s, int k, bool valid, const PairMeta& m, int lane) {
-  const FirstFit ff = group_fit<W>(s, valid, m, lane);
-  if (valid && (lane & (W - 1)) == 0) s.out[k] = fit_result(m.LA, m.LB, ff.I, ff.zd, m.gate, s.pt);
+// the pair's result word: the narrow one, or <true> the wide one with EDGE beyond the pass table from umax
+template <bool kAny>
+__device__ __forceinline__ unsigned pair_result(const ScoreArgs& s, const PairMeta& m, int I, bool zd) {
+  if constexpr (kAny)
+    return fit_result_any(m.LA, m.LB, I, zd, m.gate, s.pt, s.umax, s.n_umax);
+  else
+    return fit_result(m.LA, m.LB, I, zd, m.gate, s.pt);
 }
 
+template <int W, bool kAny>
+__device__ __forceinline__ void score_groups(const ScoreArgs& s, int k, bool valid, const PairMeta& m, int lane) {
+  const FirstFit ff = group_fit<W>(s, valid, m, lane);
+  if (valid && (lane & (W - 1)) == 0) s.out[k] = pair_result<kAny>(s, m, ff.I, ff.zd);
+}
+
+// <false>: ranks of a context without virtual reads.  <true>: real ranks on a context with virtual reads; a
+// wave that meets a pair with a list beyond FSLR_MAX_L runs its pairs one at a time, the long ones through
+// long_fit
+template <bool kAny>
 __global__ __launch_bounds__(256) void k_score_pairs(ScoreArgs s) {
   const int lane = threadIdx.x & 63;
   const int nq = (s.n_pairs + 3) >> 2;           // a wave takes pairs [4 q, 4 q + 4)
@@ -160,99 +186,37 @@ __global__ __launch_bounds__(256) void k_score_pairs(ScoreArgs s) {
     const int k0 = q << 2;
     const int k = k0 + (lane >> 4);
     const bool valid = k < s.n_pairs;
-    const PairMeta m = pair_meta(s, k, valid);
-    const bool w64 = s.wide || __ballot(m.LB > 32) != 0;
-    const bool w32 = __ballot(m.LB > 16) != 0;
-    if (w64) {
-      for (int p = 0; p < 4 && k0 + p < s.n_pairs; ++p)
-        score_groups<64>(s, k0 + p, true, pair_meta(s, k0 + p, true), lane);
-    } else if (w32) {
-      for (int p = 0; p < 4 && k0 + p < s.n_pairs; p += 2) {
-        const int k2 = k0 + p + (lane >> 5);
-        const bool v2 = k2 < s.n_pairs;
-        score_groups<32>(s, k2, v2, pair_meta(s, k2, v2), lane);
-      }
-    } else {
-      score_groups<16>(s, k, valid, m, lane);
-    }
-  }
-}
-
-// ---- real ranks on a context with virtual reads ------------------------------------------------------
-
-struct ScoreAnyArgs {
-  ScoreArgs s;                       // n_reads: the real reads
-  const int* rlen;                   // [n_real] a real read's interval count
-  const int* off2;                   // [n_real] where a long read's intervals beyond FSLR_MAX_L begin
-  const int* umax;
-  int n_umax;
-};
-
-struct AnyMeta {
-  PairMeta m;                        // offA, offB: the first chunks; LA, LB: the real lengths
-  int offA2, offB2;
-};
-
-__device__ __forceinline__ AnyMeta pair_meta_any(const ScoreAnyArgs& x, int k, bool valid) {
-  AnyMeta am{pair_meta(x.s, k, valid), 0, 0};
-  if (valid) {
-    const int ra = x.s.a[k], rb = x.s.b[k];
-    am.m.LA = x.rlen[ra];
-    am.m.LB = x.rlen[rb];
-    if (am.m.LA > FSLR_MAX_L) am.offA2 = x.off2[ra];
-    if (am.m.LB > FSLR_MAX_L) am.offB2 = x.off2[rb];
-  }
-  return am;
-}
-
-template <int W>
-__device__ __forceinline__ void score_groups_any(const ScoreAnyArgs& x, int k, bool valid, const PairMeta& m, int lane) {
-  const FirstFit ff = group_fit<W>(x.s, valid, m, lane);
-  if (valid && (lane & (W - 1)) == 0)
-    x.s.out[k] = fit_result_any(m.LA, m.LB, ff.I, ff.zd, m.gate, x.s.pt, x.umax, x.n_umax);
-}
-
-__global__ __launch_bounds__(256) void k_score_pairs_any(ScoreAnyArgs x) {
-  const ScoreArgs& s = x.s;
-  const int lane = threadIdx.x & 63;
-  const int nq = (s.n_pairs + 3) >> 2;
-  const int nw = gridDim.x * (blockDim.x >> 6);
-  for (int q = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); q < nq; q += nw) {
-    const int k0 = q << 2;
-    const int k = k0 + (lane >> 4);
-    const bool valid = k < s.n_pairs;
-    const AnyMeta am = pair_meta_any(x, k, valid);
-    const PairMeta& m = am.m;
-    if (__ballot(m.LA > FSLR_MAX_L || m.LB > FSLR_MAX_L) != 0) {
-      // a pair with a list beyond one wavefront of lanes: the wave's pairs one at a time
-      for (int p = 0; p < 4 && k0 + p < s.n_pairs; ++p) {
-        const AnyMeta a1 = pair_meta_any(x, k0 + p, true);
-        const PairMeta& m1 = a1.m;
-        if (m1.LA > FSLR_MAX_L || m1.LB > FSLR_MAX_L) {
-          int I = 0;
-          bool zd = false;
-          long_fit(m1.LA, m1.LB, ReadList{s.iv, m1.offA, a1.offA2, s.ni}, ReadList{s.iv, m1.offB, a1.offB2, s.ni}, lane,
-                   &I, &zd);
-          if (lane == 0) s.out[k0 + p] = fit_result_any(m1.LA, m1.LB, I, zd, m1.gate, s.pt, x.umax, x.n_umax);
-        } else {
-          score_groups_any<64>(x, k0 + p, true, m1, lane);
+    const PairMeta m = pair_meta<kAny>(s, k, valid);
+    if constexpr (kAny) {
+      if (__ballot(m.LA > FSLR_MAX_L || m.LB > FSLR_MAX_L) != 0) {
+        for (int p = 0; p < 4 && k0 + p < s.n_pairs; ++p) {
+          const PairMeta m1 = pair_meta<kAny>(s, k0 + p, true);
+          if (m1.LA > FSLR_MAX_L || m1.LB > FSLR_MAX_L) {
+            int I = 0;
+            bool zd = false;
+            long_fit(m1.LA, m1.LB, ReadList{s.iv, m1.offA, m1.offA2, s.ni}, ReadList{s.iv, m1.offB, m1.offB2, s.ni}, lane,
+                     &I, &zd);
+            if (lane == 0) s.out[k0 + p] = pair_result<kAny>(s, m1, I, zd);
+          } else {
+            score_groups<64, kAny>(s, k0 + p, true, m1, lane);
+          }
         }
+        continue;
       }
-      continue;
     }
     const bool w64 = s.wide || __ballot(m.LB > 32) != 0;
     const bool w32 = __ballot(m.LB > 16) != 0;
     if (w64) {
       for (int p = 0; p < 4 && k0 + p < s.n_pairs; ++p)
-        score_groups_any<64>(x, k0 + p, true, pair_meta_any(x, k0 + p, true).m, lane);
+        score_groups<64, kAny>(s, k0 + p, true, pair_meta<kAny>(s, k0 + p, true), lane);
     } else if (w32) {
       for (int p = 0; p < 4 && k0 + p < s.n_pairs; p += 2) {
         const int k2 = k0 + p + (lane >> 5);
         const bool v2 = k2 < s.n_pairs;
-        score_groups_any<32>(x, k2, v2, pair_meta_any(x, k2, v2).m, lane);
+        score_groups<32, kAny>(s, k2, v2, pair_meta<kAny>(s, k2, v2), lane);
       }
     } else {
-      score_groups_any<16>(x, k, valid, m, lane);
+      score_groups<16, kAny>(s, k, valid, m, lane);
     }
   }
 }
@@ -278,7 +242,7 @@ int ensure_scratch(fslr_ctx* c, ScoreWork* w, int64_t n) {
 }
 
 // the checked batch of either entry point, chunk after chunk.  virt: the context holds virtual reads and the
-// ranks are real ones (k_score_pairs_any, the wide result word, umax); else the lane-group kernel alone
+// ranks are real ones (k_score_pairs<true>, the wide result word, umax); else k_score_pairs<false>
 int score_run(fslr_ctx* c, const fslr_params* p, bool virt, const int32_t* umax, int32_t n_umax, int64_t n_pairs,
               const int32_t* a, const int32_t* b, int32_t* I, int32_t* U, uint8_t* flags) {
   const int64_t n_reads = virt ? c->lg_n_real : c->n;
@@ -297,8 +261,7 @@ int score_run(fslr_ctx* c, const fslr_params* p, bool virt, const int32_t* umax,
   hipStream_t st = c->stream;
   const char* wide = std::getenv("FSLR_SCORE_WIDE");       // the timing tool's comparison only
   ScoreArgs s{c->rmeta, c->iv, w->pt, w->ab, w->ab + w->cap, w->out, 0, static_cast<int>(n_reads), static_cast<int>(c->ni),
-              p->qlen_cut, p->nal_cut, wide && wide[0] == '1'};
-  ScoreAnyArgs x{s, c->lg_rlen, c->lg_off2, nullptr, 0};
+              p->qlen_cut, p->nal_cut, wide && wide[0] == '1', c->lg_rlen, c->lg_off2, nullptr, 0};
   if (virt && umax) {
     if (n_umax > w->umax_cap) {
       w->umax_cap = 0;
@@ -306,7 +269,7 @@ int score_run(fslr_ctx* c, const fslr_params* p, bool virt, const int32_t* umax,
       w->umax_cap = n_umax;
     }
     HIP_TRY(c, hipMemcpyAsync(w->umax, umax, static_cast<size_t>(n_umax) * sizeof(int), hipMemcpyHostToDevice, st));
-    x.umax = w->umax, x.n_umax = n_umax;
+    s.umax = w->umax, s.n_umax = n_umax;
   }
   int64_t step = w->cap;
   // FSLR_SCORE_CHUNK (tests): a small launch chunk, so that a small batch spans several; anything but a
@@ -327,12 +290,10 @@ int score_run(fslr_ctx* c, const fslr_params* p, bool virt, const int32_t* umax,
     HIP_TRY(c, hipMemcpyAsync(w->ab + w->cap, b + k0, mb, hipMemcpyHostToDevice, st));
     if (prof) HIP_TRY(c, hipEventRecord(w->ev[1], st));
     s.n_pairs = static_cast<int>(m);
-    if (virt) {
-      x.s.n_pairs = static_cast<int>(m);
-      k_score_pairs_any<<<grid_for((m + 3) / 4, 4, 256 * 32), 256, 0, st>>>(x);
-    } else {
-      k_score_pairs<<<grid_for((m + 3) / 4, 4, 256 * 32), 256, 0, st>>>(s);
-    }
+    if (virt)
+      k_score_pairs<true><<<grid_for((m + 3) / 4, 4, 256 * 32), 256, 0, st>>>(s);
+    else
+      k_score_pairs<false><<<grid_for((m + 3) / 4, 4, 256 * 32), 256, 0, st>>>(s);
     HIP_TRY(c, hipGetLastError());
     if (prof) HIP_TRY(c, hipEventRecord(w->ev[2], st));
     HIP_TRY(c, hipMemcpyAsync(w->host, w->out, mb, hipMemcpyDeviceToHost, st));

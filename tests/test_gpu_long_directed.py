@@ -5,8 +5,8 @@ The inputs and the expected graphs come from tests/long_ref.py, a plain restatem
 loop that tests/test_long_ref.py holds against the C oracle without a GPU.  Every comparison is exact: edges
 (a, b, I, U), forward degrees, labels and components.  Two device paths decide pairs with a long read: the
 sweep's match entries split, sorted and matched per pair (long.hip, engine 'sweep+long', overlap > 0), and the
-wave-wide general evaluator (cap.hip eval_wave, engine 'pairs', overlap <= 0: every same-chromosome cell
-matches there, so the full-block and diagonal inputs become dense).
+wave-wide general evaluator (firstfit.hpp long_fit in cap.hip's k_cap_eval, engine 'pairs', overlap <= 0:
+every same-chromosome cell matches there, so the full-block and diagonal inputs become dense).
 """
 import dataclasses
 
@@ -57,7 +57,7 @@ def _query_equals(idx, data, overlap, cuts, want, engine):
 @pytest.mark.parametrize('case', R.CASES, ids=repr)
 def test_directed_input_vs_reference(ctx, case):
     """Each input at its positive overlap with both of its cutoff lists (the sweep, k_long_split, the sort and
-    k_long_greedy) and at overlap 0.0 and -0.5 with [0.3] (k_cap_eval's eval_wave over the whole lists)."""
+    k_long_greedy) and at overlap 0.0 and -0.5 with [0.3] (k_cap_eval's long_fit over the whole lists)."""
     data = case.data()
     idx = cluster.build_interval_trees(data, ctx=ctx)
     assert idx.long is not None and int(idx.long.max()) == case.max_len
