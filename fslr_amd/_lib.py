@@ -49,7 +49,8 @@ EXPORTED = ['fslr_abi_version', 'fslr_last_error', 'fslr_ctx_create', 'fslr_ctx_
             'fslr_cluster_table', 'fslr_get_cluster_ids', 'fslr_get_cluster_members', 'fslr_assign_clusters',
             'fslr_choose_representatives', 'fslr_cluster_timings',
             'fslr_match_reads', 'fslr_match_rows', 'fslr_match_timings', 'fslr_score_pairs_any',
-            'fslr_match_reads_any', 'fslr_match_rows_any', 'fslr_append_reads', 'fslr_append_timings']
+            'fslr_match_reads_any', 'fslr_match_rows_any', 'fslr_append_reads', 'fslr_append_timings',
+            'fslr_remove_reads', 'fslr_remove_timings']
 # fslr_score_pairs' flag bits (include/fslr_hip.h)
 SCORE_GATE, SCORE_EDGE, SCORE_ZD_GATE, SCORE_ZD_OVERLAP = 1, 2, 4, 8
 # fslr_coverage_*: keys per tile of the sorted arrays, queries per chunk (include/fslr_hip.h)
@@ -59,6 +60,8 @@ COVERAGE_CHUNK = 1 << 21
 MATCH_SET = 256
 # fslr_append_reads: outputs per tile of the merge kernel (include/fslr_hip.h FSLR_APPEND_TILE)
 APPEND_TILE = 1024
+# fslr_remove_reads: data positions per tile of the data-order compaction (include/fslr_hip.h FSLR_REMOVE_TILE)
+REMOVE_TILE = 1024
 
 
 class HipUnavailable(RuntimeError):
@@ -247,6 +250,8 @@ def load(path: str = LIB_PATH):
         'fslr_match_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         'fslr_append_reads': (ctypes.c_int, [vp, ctypes.POINTER(Reads)]),
         'fslr_append_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        'fslr_remove_reads': (ctypes.c_int, [vp, i64, vp, vp]),
+        'fslr_remove_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         'fslr_coverage_build': (ctypes.c_int, [vp, i64, i32, vp, vp, vp]),
         'fslr_coverage_at': (ctypes.c_int, [vp, i64, vp, vp, vp]),
         'fslr_coverage_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
@@ -373,6 +378,7 @@ class Context:
             raise ValueError('n_alignments must lie in [0, 2**24) for the device path')
         self.n_reads = len(arrs[1])
         self.n_intervals = len(arrs[3])
+        self._read_len = np.diff(arrs[0])                 # remove_reads counts the survivors' intervals with it
 
     def load_csr_any(self, csr, iv_thr):
         """Upload a CSR whose reads may have more than FSLR_MAX_L intervals (fslr_set_reads_any: the
@@ -475,6 +481,7 @@ class Context:
         self._check(rc)
         self.n_reads += len(arrs[1])
         self.n_intervals += len(arrs[3])
+        self._read_len = np.concatenate([self._read_len, np.diff(arrs[0])])
         if len(arrs[1]):
             self.thr_gen = getattr(self, 'thr_gen', 0) + 1        # the device's threshold column changed
 
@@ -488,6 +495,34 @@ class Context:
         ms = (ctypes.c_float * 4)()
         self._check(self._L.fslr_append_timings(self._h, ms))
         return dict(zip(('upload', 'pack', 'merge', 'total'), (float(x) for x in ms)))
+
+    def remove_reads(self, keep) -> np.ndarray:
+        """fslr_remove_reads: drop the reads whose ``keep`` entry (over the ranks) is false; the survivors close
+        the gaps in rank, CSR and data order.  Returns the old rank -> new rank map (int32, -1 removed).  A
+        refused call leaves the context as it was; after a successful one build_index again."""
+        k = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+        if k.ndim != 1:
+            raise ValueError('keep is a vector over the read ranks')
+        new_rank = np.empty(k.size, np.int32)
+        rc = self._L.fslr_remove_reads(self._h, int(k.size), _ptr(k), _ptr(new_rank))
+        if rc == FSLR_ERR_HIP:
+            # a refused call and a failed allocation leave the context as it was; a device failure may leave no
+            # reads set (include/fslr_hip.h)
+            self.n_reads = self.n_intervals = 0
+        self._check(rc)
+        kept = int(np.count_nonzero(k))
+        if kept != k.size:
+            self._read_len = self._read_len[k != 0]
+            self.n_reads = kept
+            self.n_intervals = int(self._read_len.sum())
+            self.thr_gen = getattr(self, 'thr_gen', 0) + 1        # the device's threshold column changed
+        return new_rank
+
+    def remove_timings(self) -> dict:
+        """HIP-event times (ms) of the last remove_reads' phases (profiling contexts)."""
+        ms = (ctypes.c_float * 4)()
+        self._check(self._L.fslr_remove_timings(self._h, ms))
+        return dict(zip(('upload', 'maps', 'compact', 'total'), (float(x) for x in ms)))
 
     def set_thresholds(self, iv_thr):
         t = np.ascontiguousarray(iv_thr, dtype=np.int32)

@@ -43,7 +43,7 @@ from . import bam_header, ingest, multi
 from ._lib import (FSLR_MAX_L, FSLR_THR_ZERO_ALN, SCORE_EDGE, SCORE_GATE, SCORE_ZD_GATE, SCORE_ZD_OVERLAP,
                    Context)
 from .prep import (CSR, IntervalData, IntervalItem, build_csr, data_order, first_last_masks, fold_overlap_threshold,
-                   group_span, has_long_reads, mask_keep, pass_table, umax_table)
+                   group_span, has_long_reads, kept_data_rows, mask_keep, pass_table, remove_reads_csr, umax_table)
 
 __all__ = ['IntervalItem', 'keep_fillings', 'rename_chromosomes', 'chrom_to_str', 'calc_coverage',
            'filter_high_coverage', 'delete_false', 'mask_sequences2', 'prepare_data', 'build_interval_trees',
@@ -612,6 +612,53 @@ class DeviceIntervalIndex:
         ctx.build_index()
         return self
 
+    # -- fewer reads in the resident set (fslr_remove_reads) ------------------------
+    def remove(self, keep=None, qnames=None):
+        """Drop whole reads from the resident set on the device and rebuild the index: ``keep`` is a boolean
+        mask over the read ranks (True: the read stays), or ``qnames`` names the reads to drop (an unknown one
+        raises ValueError).  The survivors close the gaps in rank, CSR order and `data` list; the dense chromosome
+        ids, the qname table and the qname codes stay, so a chromosome may be left without intervals and a
+        removed qname may be appended again.  Only the mask goes to the device; the host mirrors are numpy
+        selections, O(n).  Afterwards ``self.data`` (also ``self.source``) is the list without the removed
+        reads' rows and ``self.csr`` ``prep.remove_reads_csr``'s result.  Returns the old rank -> new rank map
+        (int32, -1 for a removed read).  Keeping nothing raises ValueError."""
+        if self.long is not None:
+            raise NotImplementedError(f'remove does not take an index with reads of more than {FSLR_MAX_L} intervals')
+        if (keep is None) == (qnames is None):
+            raise TypeError('remove takes either keep (a mask over the read ranks) or qnames (the reads to drop)')
+        oc = self.csr
+        if not getattr(oc, 'start_sorted', True):
+            raise ValueError('remove needs an index built from a start-sorted data list')
+        if qnames is not None:
+            try:
+                gone = self._ranks(np.asarray(list(qnames), dtype=object))
+            except KeyError as e:
+                raise ValueError(e.args[0]) from None
+            keep = np.ones(oc.n_reads, bool)
+            keep[gone] = False
+        keep = np.asarray(keep)
+        if keep.dtype != bool or keep.shape != (oc.n_reads,):
+            raise ValueError(f'keep needs one boolean per read ({oc.n_reads})')
+        # the host mirrors first: should making them fail, the device still holds what self.data and
+        # self.csr describe
+        table = self._chrom_table()                   # the dense ids stay, so the table made for the larger set holds
+        csr, _ = remove_reads_csr(oc, keep)
+        data = self.data.select(kept_data_rows(oc, keep))
+        data._csr = csr
+        ctx = self.ctx
+        key = self.__dict__.get('_thr_key')
+        live = key is not None and key[1] == getattr(ctx, 'thr_gen', 0)
+        self.__dict__.pop('_thr_key', None)
+        new_rank = ctx.remove_reads(keep)
+        self.source = self.data = data
+        self.csr = csr
+        self._ctable = table
+        self.__dict__.pop('_rank_of', None)
+        if live:                                      # the survivors' thresholds are the ones that were installed
+            self._thr_key = (key[0], ctx.thr_gen)
+        ctx.build_index()
+        return new_rank
+
     # -- search (cluster.py:201: tree[itv.chrom].search_values(itv.start, itv.end)) ----------------
     # A query (chrom, start, end) hits the stored interval (c, s, e) iff c == chrom, s <= end and
     # e >= start (end-inclusive, superintervals search_values).  Hits are positions in the `data` list
@@ -929,6 +976,11 @@ class RowsIndex(DeviceIntervalIndex):
                                   'fslr_append_reads extends reads set by fslr_set_reads; build the index from '
                                   'prepare_data\'s result to append to it')
 
+    def remove(self, keep=None, qnames=None):
+        raise NotImplementedError('an index made from rows on the device (fslr_set_reads_rows) does not remove: '
+                                  'fslr_remove_reads compacts reads set by fslr_set_reads; build the index from '
+                                  'prepare_data\'s result to remove reads from it')
+
 
 class MultiGpuIndex:
     """What build_interval_trees returns for ``n_gpus > 1``: the prepared CSR on the host.  The ranks
@@ -959,6 +1011,10 @@ class MultiGpuIndex:
     def append(self, *args, **kwargs):
         raise NotImplementedError('a multi-GPU index lives in the rank processes and does not append '
                                   '(fslr_append_reads needs the whole index on one context); build it with n_gpus=1')
+
+    def remove(self, *args, **kwargs):
+        raise NotImplementedError('a multi-GPU index lives in the rank processes and does not remove '
+                                  '(fslr_remove_reads needs the whole index on one context); build it with n_gpus=1')
 
     def match_reads_any(self, *args, **kwargs):
         return self.match_reads(*args, **kwargs)

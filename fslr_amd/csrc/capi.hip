@@ -231,6 +231,7 @@ void fslr_ctx_destroy(fslr_ctx* c) {
   fslr_cluster_free(c);
   fslr_match_free(c);
   fslr_append_free(c);
+  fslr_remove_free(c);
   if (c->ev_ok) {
     for (auto& e : c->ev) (void)hipEventDestroy(e);
     for (auto& e : c->kev) (void)hipEventDestroy(e);

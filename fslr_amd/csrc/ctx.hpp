@@ -181,6 +181,7 @@ struct fslr_ctx {
   struct ScoreWork* scw = nullptr;       // fslr_score_pairs' scratch and its last call's times (score.hip)
   struct CoverageWork* cvw = nullptr;    // fslr_coverage_build's resident keys, the chunk staging (coverage.hip)
   struct AppendWork* apw = nullptr;      // fslr_append_reads' batch scratch and the second set of data-order buffers (append.hip)
+  struct RemoveWork* rmw = nullptr;     // fslr_remove_reads' maps and tile counts (remove.hip)
   struct MatchWork* mtw = nullptr;       // fslr_match_reads' block and chunk scratch, its last batch's rows (match.hip)
   struct ClusterWork* clw = nullptr;     // fslr_cluster_table's resident table, the assign / representatives scratch (clusters.hip)
   // reads of more than FSLR_MAX_L intervals (long.hip): the virtual-read map and the long-pair stage
@@ -241,6 +242,8 @@ void fslr_cluster_free(fslr_ctx* c);
 void fslr_match_free(fslr_ctx* c);
 // frees the append's batch scratch and its second set of data-order buffers (append.hip)
 void fslr_append_free(fslr_ctx* c);
+// frees the removal's maps and tile counts (remove.hip)
+void fslr_remove_free(fslr_ctx* c);
 
 namespace fslr {
 

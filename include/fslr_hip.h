@@ -72,6 +72,8 @@
  *   fslr_append_reads     cluster.py:109-121, 189-191 prepare_data's start-sorted `data` list and the per-read
  *                         lists for a set that grows: the lists of the union, made from the resident ones and
  *                         a new batch's (the reference rebuilds both from the whole frame)
+ *   fslr_remove_reads     cluster.py:80-86 delete_false followed by :109-121, 189-191 prepare_data for a set that
+ *                         shrinks: the lists of the frame without some reads, made from the resident ones
  *
  * Conventions: plain C types, caller-owned host arrays, library-owned device
  * memory behind an opaque context.  Every function returns FSLR_OK (0) or an
@@ -829,6 +831,44 @@ int  fslr_match_rows_any(fslr_ctx *ctx, int32_t *partner, int32_t *I, int32_t *U
 #define FSLR_APPEND_TILE 1024
 int  fslr_append_reads(fslr_ctx *ctx, const fslr_reads *reads);
 int  fslr_append_timings(fslr_ctx *ctx, float *ms);
+
+/* ---- Removing reads from a resident set --------------------------------------------------------------
+ * fslr_remove_reads drops whole reads from the resident set on the device, where until now the only route was
+ * fslr_set_reads of the survivors.  keep[r] != 0 means resident read r stays; n must equal the resident read
+ * count.  new_rank (NULL or int32[n]) receives the old rank -> new rank map, -1 for a removed read.
+ * After a successful call the context holds the kept reads with the gaps closed: a survivor's new rank is the
+ * number of kept reads of lower rank, its intervals keep their order at CSR offset = the sum of the kept lower
+ * reads' lengths, and a kept interval at data position d moves to #{kept elements before d}.  n_chroms and
+ * the dense chromosome ids stay (a chromosome may be left without intervals).  Every resident buffer and
+ * host-side count then equals, byte for byte, what fslr_set_reads gives for that compacted CSR with the
+ * survivors' thresholds as currently set; the same bytes on every run.  The threshold mode and the
+ * aln_size == 0 mark are those of the survivors, not carried over: removing the only reads that held a general
+ * threshold or an aln_size == 0 interval lets FSLR_ENGINE_AUTO pick the sweep again.  As after fslr_set_reads
+ * and fslr_append_reads: no index is built (fslr_build_index next), the saved search, match and score batches,
+ * the position plan and the query-reuse state belong to the old reads; the coverage set and the cluster table
+ * are left as fslr_append_reads leaves them.
+ * Cost: H2D of the n keep bytes; D2H of n_chroms counts, a few status words and, on request, new_rank (and the
+ * n read lengths, one byte each, when the context holds an aln_size == 0 interval: the host's marks of those
+ * are compacted by them).  No resident column crosses the link and there is no host pass over resident
+ * intervals otherwise.  Syncs.
+ * Atomic: everything is validated and everything is allocated before any resident buffer is written.
+ * FSLR_ERR_INVALID: n differs from the resident count, keep is NULL, nothing would be kept.  FSLR_ERR_STATE,
+ * named in the message: no reads set; reads set without iv_data_pos; reads made from rows; virtual reads;
+ * n_shards > 1; a chromosome or position filter active.  FSLR_ERR_NOMEM.  All of these leave the context as it
+ * was: the same reads, the index still built if it was, the saved batches readable.  Only a device failure
+ * after that point (FSLR_ERR_HIP) leaves no reads set.  Keeping every read is valid, changes nothing (no
+ * generation moves) and returns the identity map.
+ * Memory: the data order is compacted into the second set of data-order buffers fslr_append_reads keeps (28 B
+ * per interval of capacity, allocated by whichever call comes first) and the sets swap; the CSR order is
+ * compacted into index-build scratch of the same size, which is swapped with the resident buffers (the index
+ * is rebuilt anyway); the maps take 10 B per read.  Buffers never shrink.
+ * FSLR_REMOVE_TILE: data positions per tile of the data-order compaction.
+ * fslr_remove_timings (fslr_set_profiling 1 or 2): HIP-event times (ms) of the last fslr_remove_reads that
+ * removed something, ms[0..3] = upload, maps (flags, tile counts, scans, read maps), compaction (data order
+ * and CSR order), first to last event. */
+#define FSLR_REMOVE_TILE 1024
+int  fslr_remove_reads(fslr_ctx *ctx, int64_t n, const uint8_t *keep, int32_t *new_rank);
+int  fslr_remove_timings(fslr_ctx *ctx, float *ms);
 
 /* Device-side views for collectives (e.g. RCCL all_gather of labels). */
 int  fslr_labels_device_ptr(fslr_ctx *ctx, void **dptr);
