@@ -50,7 +50,7 @@ EXPORTED = ['fslr_abi_version', 'fslr_last_error', 'fslr_ctx_create', 'fslr_ctx_
             'fslr_choose_representatives', 'fslr_cluster_timings',
             'fslr_match_reads', 'fslr_match_rows', 'fslr_match_timings', 'fslr_score_pairs_any',
             'fslr_match_reads_any', 'fslr_match_rows_any', 'fslr_append_reads', 'fslr_append_timings',
-            'fslr_remove_reads', 'fslr_remove_timings']
+            'fslr_remove_reads', 'fslr_remove_timings', 'fslr_append_reads_any', 'fslr_remove_reads_any']
 # fslr_score_pairs' flag bits (include/fslr_hip.h)
 SCORE_GATE, SCORE_EDGE, SCORE_ZD_GATE, SCORE_ZD_OVERLAP = 1, 2, 4, 8
 # fslr_coverage_*: keys per tile of the sorted arrays, queries per chunk (include/fslr_hip.h)
@@ -252,6 +252,8 @@ def load(path: str = LIB_PATH):
         'fslr_append_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         'fslr_remove_reads': (ctypes.c_int, [vp, i64, vp, vp]),
         'fslr_remove_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        'fslr_append_reads_any': (ctypes.c_int, [vp, ctypes.POINTER(Reads)]),
+        'fslr_remove_reads_any': (ctypes.c_int, [vp, i64, vp, vp]),
         'fslr_coverage_build': (ctypes.c_int, [vp, i64, i32, vp, vp, vp]),
         'fslr_coverage_at': (ctypes.c_int, [vp, i64, vp, vp, vp]),
         'fslr_coverage_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
@@ -395,6 +397,7 @@ class Context:
         L = np.diff(arrs[0].astype(np.int64))
         self.n_reads = int(len(arrs[1]) + np.maximum((L + FSLR_MAX_L - 1) // FSLR_MAX_L - 1, 0).sum())
         self.n_intervals = len(arrs[3])
+        self._read_len = L.astype(np.int32)               # the REAL reads' lengths (the _any calls count with them)
 
     def rows_upload(self, cols, n_codes, n_chrom_ids):
         """fslr_rows_upload: keep_fillings' rows (``cols``: int64 columns chrom, start, end, aln, qcode,
@@ -489,6 +492,52 @@ class Context:
         """append_reads of a ``fslr_amd.prep.CSR`` whose ``iv_chrom`` holds the resident dense ids."""
         self.append_reads(csr.read_off, csr.read_qlen2, csr.read_nal, csr.iv_chrom, csr.iv_start, csr.iv_end, iv_thr,
                           csr.n_chroms, csr.data_pos)
+
+    def append_reads_any(self, read_off, read_qlen2, read_nal, iv_chrom, iv_start, iv_end, iv_thr, n_chroms, iv_data_pos):
+        """fslr_append_reads_any: append_reads for a batch whose reads may have up to FSLR_MAX_ANY_L intervals
+        and for a context loaded with load_csr_any.  The batch is a REAL CSR; ``n_reads`` then counts the
+        virtual reads as load_csr_any does.  A refused batch leaves the context as it was."""
+        arrs = [np.ascontiguousarray(x, dtype=np.int32) for x in
+                (read_off, read_qlen2, read_nal, iv_chrom, iv_start, iv_end, iv_thr)]
+        dp = None if iv_data_pos is None else np.ascontiguousarray(iv_data_pos, dtype=np.int32)
+        r = Reads(len(arrs[1]), len(arrs[3]), int(n_chroms), *(_ptr(a) for a in arrs),
+                  _ptr(dp) if dp is not None else None)
+        rc = self._L.fslr_append_reads_any(self._h, ctypes.byref(r))
+        if rc == FSLR_ERR_HIP:
+            self.n_reads = self.n_intervals = 0
+        self._check(rc)
+        L = np.diff(arrs[0].astype(np.int64))
+        self.n_reads += int(len(arrs[1]) + np.maximum((L + FSLR_MAX_L - 1) // FSLR_MAX_L - 1, 0).sum())
+        self.n_intervals += len(arrs[3])
+        self._read_len = np.concatenate([self._read_len, L.astype(np.int32)])
+        if len(arrs[1]):
+            self.thr_gen = getattr(self, 'thr_gen', 0) + 1        # the device's threshold column changed
+
+    def append_csr_any(self, csr, iv_thr):
+        """append_reads_any of a ``fslr_amd.prep.CSR`` whose ``iv_chrom`` holds the resident dense ids."""
+        self.append_reads_any(csr.read_off, csr.read_qlen2, csr.read_nal, csr.iv_chrom, csr.iv_start, csr.iv_end,
+                              iv_thr, csr.n_chroms, csr.data_pos)
+
+    def remove_reads_any(self, keep) -> np.ndarray:
+        """fslr_remove_reads_any: remove_reads with ``keep`` over the REAL read ranks of a context that may hold
+        reads of more than FSLR_MAX_L intervals (a removed read loses all its chunks).  Returns the old real
+        rank -> new real rank map (int32, -1 removed)."""
+        k = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+        if k.ndim != 1:
+            raise ValueError('keep is a vector over the read ranks')
+        new_rank = np.empty(k.size, np.int32)
+        rc = self._L.fslr_remove_reads_any(self._h, int(k.size), _ptr(k), _ptr(new_rank))
+        if rc == FSLR_ERR_HIP:
+            self.n_reads = self.n_intervals = 0
+        self._check(rc)
+        kept = int(np.count_nonzero(k))
+        if kept != k.size:
+            L = self._read_len[k != 0].astype(np.int64)
+            self._read_len = self._read_len[k != 0]
+            self.n_reads = int(kept + np.maximum((L + FSLR_MAX_L - 1) // FSLR_MAX_L - 1, 0).sum())
+            self.n_intervals = int(L.sum())
+            self.thr_gen = getattr(self, 'thr_gen', 0) + 1        # the device's threshold column changed
+        return new_rank
 
     def append_timings(self) -> dict:
         """HIP-event times (ms) of the last append_reads' phases (profiling contexts)."""

@@ -534,9 +534,22 @@ class DeviceIntervalIndex:
         Afterwards ``self.data`` (also ``self.source``) is the merged IntervalData and ``self.csr`` the
         concatenated CSR with the merged data positions.  A read is a whole list: a qname that is already
         resident raises ValueError.  Chromosome values the index has not seen take the next dense ids in
-        ascending value."""
-        if self.long is not None:
-            raise NotImplementedError(f'append does not take an index with reads of more than {FSLR_MAX_L} intervals')
+        ascending value.  A read of more than 64 intervals, on either side, raises NotImplementedError here:
+        ``append_any`` takes those."""
+        return self._append(new_data, False)
+
+    def append_any(self, new_data):
+        """``append`` for reads of any length (fslr_append_reads_any): the index may hold reads
+        of more than 64 intervals and ``new_data`` may bring some (up to 4096 intervals each).  On the device
+        the resident chunk reads are relocated around the batch; afterwards the index is what
+        ``build_interval_trees`` of the union gives, with the resident reads first.  Without a long read on
+        either side it is ``append``."""
+        return self._append(new_data, True)
+
+    def _append(self, new_data, any_length):
+        if self.long is not None and not any_length:
+            raise NotImplementedError(f'append does not take an index with reads of more than {FSLR_MAX_L} intervals '
+                                      f'(append_any does)')
         if not isinstance(new_data, IntervalData):
             new_data = IntervalData.from_items(new_data)
         old, oc = self.data, self.csr
@@ -547,8 +560,10 @@ class DeviceIntervalIndex:
         nc = build_csr(new_data)
         if not nc.start_sorted:
             raise ValueError('the new data list is not in start order (prepare_data sorts it)')
-        if has_long_reads(nc):
-            raise NotImplementedError(f'append does not take a read of more than {FSLR_MAX_L} intervals')
+        if has_long_reads(nc) and not any_length:
+            raise NotImplementedError(f'append does not take a read of more than {FSLR_MAX_L} intervals (append_any does)')
+        # a read of more than FSLR_MAX_L intervals on either side: fslr_append_reads_any
+        any_length = any_length and (self.long is not None or has_long_reads(nc))
         names = lambda q: q if isinstance(q, np.ndarray) else q[np.arange(len(q))]
         old_names, new_names = names(old.qnames), names(new_data.qnames)
         resident = set(old_names[np.asarray(oc.read_qcode, np.int64)].tolist())
@@ -602,9 +617,13 @@ class DeviceIntervalIndex:
         self.__dict__.pop('_thr_key', None)
         thr = fold_overlap_threshold(nc.iv_aln, key[0]) if live else \
             np.where(nc.iv_aln == 0, FSLR_THR_ZERO_ALN, 0).astype(np.int32)
-        ctx.append_csr(batch, thr)
+        if any_length:
+            ctx.append_csr_any(batch, thr)
+        else:
+            ctx.append_csr(batch, thr)
         self.source = self.data = data
         self.csr = data._csr
+        self.long = np.diff(np.asarray(self.csr.read_off, np.int64)).astype(np.int32) if has_long_reads(self.csr) else None
         self.__dict__.pop('_ctable', None)
         self.__dict__.pop('_rank_of', None)
         if live:
@@ -621,9 +640,20 @@ class DeviceIntervalIndex:
         removed qname may be appended again.  Only the mask goes to the device; the host mirrors are numpy
         selections, O(n).  Afterwards ``self.data`` (also ``self.source``) is the list without the removed
         reads' rows and ``self.csr`` ``prep.remove_reads_csr``'s result.  Returns the old rank -> new rank map
-        (int32, -1 for a removed read).  Keeping nothing raises ValueError."""
-        if self.long is not None:
-            raise NotImplementedError(f'remove does not take an index with reads of more than {FSLR_MAX_L} intervals')
+        (int32, -1 for a removed read).  Keeping nothing raises ValueError.  An index with reads of more than 64
+        intervals raises NotImplementedError here: ``remove_any`` takes it."""
+        return self._remove(keep, qnames, False)
+
+    def remove_any(self, keep=None, qnames=None):
+        """``remove`` for an index that may hold reads of more than 64 intervals (fslr_remove_reads_any, DESIGN.md
+        §13.7): ``keep`` and the returned map are over the real read ranks, a removed read loses all its chunks,
+        and once no long read is left the index is a plain one.  Without a long read it is ``remove``."""
+        return self._remove(keep, qnames, True)
+
+    def _remove(self, keep, qnames, any_length):
+        if self.long is not None and not any_length:
+            raise NotImplementedError(f'remove does not take an index with reads of more than {FSLR_MAX_L} intervals '
+                                      f'(remove_any does)')
         if (keep is None) == (qnames is None):
             raise TypeError('remove takes either keep (a mask over the read ranks) or qnames (the reads to drop)')
         oc = self.csr
@@ -649,9 +679,11 @@ class DeviceIntervalIndex:
         key = self.__dict__.get('_thr_key')
         live = key is not None and key[1] == getattr(ctx, 'thr_gen', 0)
         self.__dict__.pop('_thr_key', None)
-        new_rank = ctx.remove_reads(keep)
+        # with a read of more than FSLR_MAX_L intervals resident: fslr_remove_reads_any
+        new_rank = ctx.remove_reads_any(keep) if self.long is not None else ctx.remove_reads(keep)
         self.source = self.data = data
         self.csr = csr
+        self.long = np.diff(np.asarray(csr.read_off, np.int64)).astype(np.int32) if has_long_reads(csr) else None
         self._ctable = table
         self.__dict__.pop('_rank_of', None)
         if live:                                      # the survivors' thresholds are the ones that were installed
@@ -976,10 +1008,14 @@ class RowsIndex(DeviceIntervalIndex):
                                   'fslr_append_reads extends reads set by fslr_set_reads; build the index from '
                                   'prepare_data\'s result to append to it')
 
+    append_any = append
+
     def remove(self, keep=None, qnames=None):
         raise NotImplementedError('an index made from rows on the device (fslr_set_reads_rows) does not remove: '
                                   'fslr_remove_reads compacts reads set by fslr_set_reads; build the index from '
                                   'prepare_data\'s result to remove reads from it')
+
+    remove_any = remove
 
 
 class MultiGpuIndex:
@@ -1015,6 +1051,8 @@ class MultiGpuIndex:
     def remove(self, *args, **kwargs):
         raise NotImplementedError('a multi-GPU index lives in the rank processes and does not remove '
                                   '(fslr_remove_reads needs the whole index on one context); build it with n_gpus=1')
+
+    append_any, remove_any = append, remove
 
     def match_reads_any(self, *args, **kwargs):
         return self.match_reads(*args, **kwargs)

@@ -22,7 +22,7 @@ using namespace fslr;
 void fslr_append_free(fslr_ctx* c) {
   AppendWork* w = c->apw;
   if (!w) return;
-  void* bufs[] = {w->cols, w->rmeta, w->rlen8, w->iv, w->inv, w->dch, w->drc, w->dgt, w->w64, w->alt_ch, w->alt_rec, w->alt_gate};
+  void* bufs[] = {w->cols, w->rmeta, w->rlen8, w->iv, w->inv, w->dch, w->drc, w->dgt, w->w64, w->alt_ch, w->alt_rec, w->alt_gate, w->maps, w->rl_out};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (w->ev_ok)
@@ -43,12 +43,15 @@ constexpr int kTile = FSLR_APPEND_TILE;
 //   - a mixed tile stages its keys in LDS, ranks every element against the other list's run there, and
 //     writes its outputs in order from the source index each output position recorded.
 // newpos[i] (i < ni) = the merged position of resident data position i, newpos[ni + j] that of the batch's j.
+// tag_n, tag_m: a resident record's tag `read << 6 | j` with read >= tag_n moves up by tag_m reads
+// (fslr_append_reads_any: the resident further chunks behind the batch's first chunks; tag_m 0: today's bytes).
 __global__ __launch_bounds__(256) void k_append_merge(const unsigned* __restrict__ rch, const int4* __restrict__ rrec,
                                                       const int2* __restrict__ rgate, int ni,
                                                       const unsigned* __restrict__ nch, const int4* __restrict__ nrec,
                                                       const int2* __restrict__ ngate, int mi,
                                                       unsigned* __restrict__ och, int4* __restrict__ orec,
-                                                      int2* __restrict__ ogate, int* __restrict__ newpos) {
+                                                      int2* __restrict__ ogate, int* __restrict__ newpos,
+                                                      int tag_n, int tag_m) {
   __shared__ int split[2];
   __shared__ int key[kTile];
   __shared__ int src[kTile];
@@ -77,7 +80,9 @@ __global__ __launch_bounds__(256) void k_append_merge(const unsigned* __restrict
       for (int t = tid; t < len; t += blockDim.x) {
         FSLR_BOUND(i0 + t, ni);
         FSLR_BOUND(d0 + t, total);
-        orec[d0 + t] = rrec[i0 + t];
+        int4 rec = rrec[i0 + t];
+        rec.w = anyidx::retag(rec.w, tag_n, tag_m);
+        orec[d0 + t] = rec;
         ogate[d0 + t] = rgate[i0 + t];
         och[d0 + t] = rch[i0 + t];
         newpos[i0 + t] = d0 + t;
@@ -135,7 +140,9 @@ __global__ __launch_bounds__(256) void k_append_merge(const unsigned* __restrict
         FSLR_BOUND(d0 + p, total);
         if (t < na) {
           FSLR_BOUND(i0 + t, ni);
-          orec[d0 + p] = rrec[i0 + t];
+          int4 rec = rrec[i0 + t];
+          rec.w = anyidx::retag(rec.w, tag_n, tag_m);
+          orec[d0 + p] = rec;
           ogate[d0 + p] = rgate[i0 + t];
           och[d0 + p] = rch[i0 + t];
         } else {
@@ -200,12 +207,7 @@ int ensure_batch(fslr_ctx* c, AppendWork* w, int64_t m, int64_t mi, int n_chroms
   return FSLR_OK;
 }
 
-// once memory is there nothing but the device can fail; what is then half written is not a set of reads
-int broken(fslr_ctx* c, int rc) {
-  c->reads_set = false;
-  c->index_built = false;
-  return rc;
-}
+int broken(fslr_ctx* c, int rc) { return reads_broken(c, rc); }
 
 #define APP_TRY(ctx, expr)                                                                                    \
   do {                                                                                                        \
@@ -216,29 +218,46 @@ int broken(fslr_ctx* c, int rc) {
 
 }  // namespace
 
-extern "C" {
+// once memory is there nothing but the device can fail; what is then half written is not a set of reads
+int fslr::reads_broken(fslr_ctx* c, int rc) {
+  c->reads_set = false;
+  c->index_built = false;
+  return rc;
+}
 
-int fslr_append_reads(fslr_ctx* c, const fslr_reads* r) {
-  if (!c || !r) return FSLR_ERR_INVALID;
-  if (!c->reads_set) return fail(c, FSLR_ERR_STATE, "fslr_append_reads: no reads set (fslr_set_reads first)");
+// the states neither append takes, each named; virt: virtual reads are fine (fslr_append_reads_any)
+int fslr::append_state(fslr_ctx* c, const std::string& who, bool virt) {
+  if (!c->reads_set) return fail(c, FSLR_ERR_STATE, who + ": no reads set (fslr_set_reads first)");
   if (c->rows_set)
-    return fail(c, FSLR_ERR_STATE, "fslr_append_reads: the reads were made from rows (fslr_set_reads_rows), which it does not extend");
-  if (c->lg_set || !c->lg_perm.empty())
-    return fail(c, FSLR_ERR_STATE, "fslr_append_reads: the context holds virtual reads (fslr_set_reads_any / fslr_set_long_reads: "
+    return fail(c, FSLR_ERR_STATE, who + ": the reads were made from rows (fslr_set_reads_rows), which it does not extend");
+  if (!virt && (c->lg_set || !c->lg_perm.empty()))
+    return fail(c, FSLR_ERR_STATE, who + ": the context holds virtual reads (fslr_set_reads_any / fslr_set_long_reads: "
                                    "reads of more than " + std::to_string(FSLR_MAX_L) + " intervals), which it does not extend");
+  if (virt && c->lg_set && c->lg_perm.empty())
+    return fail(c, FSLR_ERR_STATE, who + ": the virtual reads were made by the caller (fslr_set_long_reads), not by "
+                                   "fslr_set_reads_any: their real CSR is not known here");
   if (!c->have_data_pos)
-    return fail(c, FSLR_ERR_STATE, "fslr_append_reads: the reads were set without iv_data_pos (no start-sorted data list to merge into)");
-  if (c->n_shards > 1) return fail(c, FSLR_ERR_STATE, "fslr_append_reads: n_shards > 1 (fslr_set_shard): multi-GPU contexts do not append");
+    return fail(c, FSLR_ERR_STATE, who + ": the reads were set without iv_data_pos (no start-sorted data list to merge into)");
+  if (c->n_shards > 1) return fail(c, FSLR_ERR_STATE, who + ": n_shards > 1 (fslr_set_shard): multi-GPU contexts do not append");
   if (c->filter_active || c->pf_on)
-    return fail(c, FSLR_ERR_STATE, "fslr_append_reads: a chromosome or position filter is active");
+    return fail(c, FSLR_ERR_STATE, who + ": a chromosome or position filter is active");
+  return FSLR_OK;
+}
+
+// plan null: fslr_append_reads.  Otherwise r is the batch's virtual CSR (plan->s.m first chunks, then plan->s.e
+// further chunks) and the resident set is relocated around it (any.hip).
+int fslr::append_core(fslr_ctx* c, const fslr_reads* r, const AnyPlan* plan, const char* who_c) {
+  const std::string who(who_c);
+  if (!c || !r) return FSLR_ERR_INVALID;
+  if (int rc = append_state(c, who, plan != nullptr)) return rc;
   const int64_t n = c->n, ni = c->ni, m = r->n_reads, mi = r->n_intervals;
   if (m < 0 || mi < 0 || n + m >= FSLR_MAX_READS || ni + mi >= (int64_t(1) << 31) - 1)
     return fail(c, FSLR_ERR_INVALID, "read / interval count out of range");
   if (r->n_chroms < 1 || r->n_chroms >= (1 << 24)) return fail(c, FSLR_ERR_INVALID, "n_chroms out of range");
-  if (r->n_chroms < c->n_chroms) return fail(c, FSLR_ERR_INVALID, "fslr_append_reads: n_chroms below the resident value");
+  if (r->n_chroms < c->n_chroms) return fail(c, FSLR_ERR_INVALID, who + ": n_chroms below the resident value");
   if (!r->read_off || !r->read_qlen2 || !r->read_nal || !r->iv_chrom || !r->iv_start || !r->iv_end || !r->iv_thr)
     return fail(c, FSLR_ERR_INVALID, "null array");
-  if (!r->iv_data_pos) return fail(c, FSLR_ERR_INVALID, "fslr_append_reads: iv_data_pos is required");
+  if (!r->iv_data_pos) return fail(c, FSLR_ERR_INVALID, who + ": iv_data_pos is required");
   if (r->read_off[0] != 0 || r->read_off[m] != mi) return fail(c, FSLR_ERR_INVALID, "read_off does not span intervals");
   if (m == 0) return FSLR_OK;                    // nothing to add: no generation moves
   HIP_TRY(c, hipSetDevice(c->device));
@@ -251,6 +270,15 @@ int fslr_append_reads(fslr_ctx* c, const fslr_reads* r) {
     w->ev_ok = true;
   }
   if (int rc = ensure_batch(c, w, m, mi, r->n_chroms)) return rc;
+  const int64_t n_real = plan ? plan->s.n : n, m_real = plan ? plan->s.m : m;
+  if (plan) {
+    const int64_t maps = 2 * m + 2 * m_real;
+    if (maps > w->maps_cap) {
+      w->maps_cap = 0;
+      if (int rc = dalloc(c, &w->maps, static_cast<size_t>(maps + maps / 4))) return rc;
+      w->maps_cap = maps + maps / 4;
+    }
+  }
   hipStream_t st = c->stream;
   // ---- the batch: up as it is, validated and packed in scratch; nothing resident is written ----------
   int* d_off = w->cols;
@@ -277,6 +305,16 @@ int fslr_append_reads(fslr_ctx* c, const fslr_reads* r) {
     HIP_TRY(c, hipMemcpyAsync(d_th, r->iv_thr, ib, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(d_dp, r->iv_data_pos, ib, hipMemcpyHostToDevice, st));
   }
+  int* d_bvreal = w->maps;                       // (plan) vreal [m] | vbase [m] | rlen [m_real] | off2 [m_real]
+  int* d_bvbase = d_bvreal + m;
+  int* d_brlen = d_bvbase + m;
+  int* d_boff2 = d_brlen + m_real;
+  if (plan) {
+    HIP_TRY(c, hipMemcpyAsync(d_bvreal, plan->b_vreal, mb, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(d_bvbase, plan->b_vbase, mb, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(d_brlen, plan->b_rlen, static_cast<size_t>(m_real) * sizeof(int), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(d_boff2, plan->b_off2, static_cast<size_t>(m_real) * sizeof(int), hipMemcpyHostToDevice, st));
+  }
   if (prof) HIP_TRY(c, hipEventRecord(w->ev[1], st));
   // the reads' own checks on the host, in index order (fslr_set_reads' codes: 3 length, 4 n_alignments, 5 qlen2)
   int bad = 0;
@@ -301,6 +339,13 @@ int fslr_append_reads(fslr_ctx* c, const fslr_reads* r) {
   ua.reads_ok = bad == 0;
   ua.rank_base = static_cast<int>(n);
   ua.off_base = static_cast<int>(ni);
+  if (plan) {                                    // first chunks behind the resident ones, further chunks at the end
+    ua.rank_base = plan->s.n;
+    ua.off_base = plan->s.o1;
+    ua.split = plan->s.m;
+    ua.rank_base2 = plan->s.V;
+    ua.off_base2 = plan->s.ni;
+  }
   ua.iv = w->iv;
   ua.rmeta = w->rmeta;
   ua.rlen8 = w->rlen8;
@@ -344,21 +389,78 @@ int fslr_append_reads(fslr_ctx* c, const fslr_reads* r) {
   }
   // ... and every buffer that has to grow, allocated before any is freed (the same holds for a failure here)
   if (int rc = grow_capacity_keep(c, cap_n, cap_ni, r->n_chroms)) return rc;
+  // (plan) the relocated read lengths and the new virtual-read maps, beside the old ones until they are written
+  struct NewMaps {                               // freed on every way out but the one that installs them
+    int* lg[4] = {nullptr, nullptr, nullptr, nullptr};       // vreal, vbase [need_n] | rlen, off2 [n_real + m_real]
+    int* umax = nullptr;
+    ~NewMaps() {
+      for (int* p : lg)
+        if (p) (void)hipFree(p);
+      if (umax) (void)hipFree(umax);
+    }
+  } fresh;
+  int** lg_new = fresh.lg;
+  int*& umax_new = fresh.umax;
+  if (plan) {
+    if (need_n > w->rl_cap) {
+      w->rl_cap = 0;
+      if (int rc = dalloc(c, &w->rl_out, static_cast<size_t>(cap_n))) return rc;
+      w->rl_cap = cap_n;
+    }
+    const size_t cnt[4] = {static_cast<size_t>(need_n), static_cast<size_t>(need_n), static_cast<size_t>(n_real + m_real),
+                           static_cast<size_t>(n_real + m_real)};
+    for (int k = 0; k < 4; ++k)
+      if (hipMalloc(reinterpret_cast<void**>(&lg_new[k]), cnt[k] * sizeof(int)) != hipSuccess) {
+        lg_new[k] = nullptr;
+        return fail(c, FSLR_ERR_NOMEM, who + ": hipMalloc of the virtual-read maps");
+      }
+    if (!c->lg_set) {                            // a plain context turns virtual: the placeholder cutoffs of a fresh upload
+      if (hipMalloc(reinterpret_cast<void**>(&umax_new), static_cast<size_t>(plan->max_len) * sizeof(int)) != hipSuccess) {
+        umax_new = nullptr;
+        return fail(c, FSLR_ERR_NOMEM, who + ": hipMalloc of the cutoff table");
+      }
+    }
+    if (!c->lg_cnt)
+      if (int rc = dalloc(c, &c->lg_cnt, 4)) return rc;
+  }
   // from here the index scratch is reused and the resident buffers are written
   c->index_built = false;
   c->hooked = false;
   if (prof) APP_TRY(c, hipEventRecord(w->ev[3], st));
-  APP_TRY(c, hipMemcpyAsync(c->rmeta + n, w->rmeta, static_cast<size_t>(m) * sizeof(int4), hipMemcpyDeviceToDevice, st));
-  APP_TRY(c, hipMemcpyAsync(c->rlen8 + n, w->rlen8, static_cast<size_t>(m), hipMemcpyDeviceToDevice, st));
-  if (mi) APP_TRY(c, hipMemcpyAsync(c->iv + ni, w->iv, static_cast<size_t>(mi) * sizeof(int4), hipMemcpyDeviceToDevice, st));
+  if (!plan) {
+    APP_TRY(c, hipMemcpyAsync(c->rmeta + n, w->rmeta, static_cast<size_t>(m) * sizeof(int4), hipMemcpyDeviceToDevice, st));
+    APP_TRY(c, hipMemcpyAsync(c->rlen8 + n, w->rlen8, static_cast<size_t>(m), hipMemcpyDeviceToDevice, st));
+    if (mi) APP_TRY(c, hipMemcpyAsync(c->iv + ni, w->iv, static_cast<size_t>(mi) * sizeof(int4), hipMemcpyDeviceToDevice, st));
+  }
   int* newpos = c->vals;                         // [ni + mi] index-build scratch (the index is rebuilt anyway)
   const int64_t tiles = (need_ni + kTile - 1) / kTile;
   if (need_ni) {
     k_append_merge<<<static_cast<int>(std::min<int64_t>(tiles, 256 * 16)), 256, 0, st>>>(
         c->dchrom, c->drec, c->dgate, static_cast<int>(ni), w->dch, w->drc, w->dgt, static_cast<int>(mi), w->alt_ch,
-        w->alt_rec, w->alt_gate, newpos);
-    k_append_datapos<<<grid_for(need_ni), 256, 0, st>>>(c->data_pos, static_cast<int>(ni), d_dp, static_cast<int>(mi), newpos);
+        w->alt_rec, w->alt_gate, newpos, plan ? plan->s.n : 0x7fffffff, plan ? plan->s.m : 0);
+    if (!plan)
+      k_append_datapos<<<grid_for(need_ni), 256, 0, st>>>(c->data_pos, static_cast<int>(ni), d_dp, static_cast<int>(mi), newpos);
     APP_TRY(c, hipGetLastError());
+  }
+  if (plan) {
+    // the rows, the reads and the maps of the four groups (any_idx.hpp) into index-build scratch and the new
+    // maps: never in place, a resident chunk row's destination is another's source
+    AnyReloc a{};
+    a.s = plan->s;
+    a.rmeta = c->rmeta, a.rlen8 = c->rlen8, a.iv = c->iv, a.data_pos = c->data_pos;
+    if (c->lg_set) a.vreal = c->lg_vreal, a.vbase = c->lg_vbase, a.rlen = c->lg_rlen, a.off2 = c->lg_off2;
+    a.b_rmeta = w->rmeta, a.b_rlen8 = w->rlen8, a.b_iv = w->iv, a.b_dp = d_dp;
+    a.b_vreal = d_bvreal, a.b_vbase = d_bvbase, a.b_rlen = d_brlen, a.b_off2 = d_boff2;
+    a.newpos = newpos;
+    a.rmeta_out = c->lbounds, a.rlen8_out = w->rl_out, a.iv_out = c->idx4, a.dp_out = c->vals2;
+    a.vreal_out = lg_new[0], a.vbase_out = lg_new[1], a.rlen_out = lg_new[2], a.off2_out = lg_new[3];
+    c->lb_gen = -1;                              // the length gate's ranges belonged to the old reads anyway
+    hipError_t e = launch_any_relocate(a, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->rlen8, w->rl_out, static_cast<size_t>(need_n), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess && umax_new) e = hipMemsetAsync(umax_new, 0, static_cast<size_t>(plan->max_len) * sizeof(int), st);
+    if (e != hipSuccess) {
+      return broken(c, fail(c, FSLR_ERR_HIP, who + ": relocation: " + hipGetErrorString(e)));
+    }
   }
   if (prof) APP_TRY(c, hipEventRecord(w->ev[4], st));
   // chromosome ranges of the (chrom, start)-sorted index from the summed counts, as fslr_set_reads makes them
@@ -377,8 +479,47 @@ int fslr_append_reads(fslr_ctx* c, const fslr_reads* r) {
   std::swap(c->drec, w->alt_rec);
   std::swap(c->dgate, w->alt_gate);
   w->alt_cap = old_cap_ni;                       // what the context's buffers were allocated for, at least
-  c->aln_zero_host.resize(static_cast<size_t>(need_ni), 0);
-  for (int64_t k = 0; k < mi; ++k) c->aln_zero_host[static_cast<size_t>(ni + k)] = r->iv_thr[k] == FSLR_THR_ZERO_ALN;
+  if (!plan) {
+    c->aln_zero_host.resize(static_cast<size_t>(need_ni), 0);
+    for (int64_t k = 0; k < mi; ++k) c->aln_zero_host[static_cast<size_t>(ni + k)] = r->iv_thr[k] == FSLR_THR_ZERO_ALN;
+  } else {
+    std::swap(c->rmeta, c->lbounds);
+    std::swap(c->iv, c->idx4);
+    std::swap(c->data_pos, c->vals2);
+    int** slot[4] = {&c->lg_vreal, &c->lg_vbase, &c->lg_rlen, &c->lg_off2};
+    for (int k = 0; k < 4; ++k) {
+      if (*slot[k]) (void)hipFree(*slot[k]);
+      *slot[k] = lg_new[k];
+      lg_new[k] = nullptr;
+    }
+    if (umax_new) {
+      if (c->lg_umax) (void)hipFree(c->lg_umax);
+      c->lg_umax = umax_new;
+      umax_new = nullptr;
+      c->lg_n_umax = plan->max_len;
+    }
+    // the host's marks and the virtual -> real interval map, in the rows' four groups
+    const anyidx::Shape& s = plan->s;
+    std::vector<unsigned char> zero(static_cast<size_t>(need_ni));
+    std::vector<int> perm(static_cast<size_t>(need_ni));
+    const bool ident = c->lg_perm.empty();
+    for (int64_t k = 0; k < need_ni; ++k) {
+      const int src = anyidx::row_source(static_cast<int>(k), s);
+      if (src >= 0) {
+        zero[static_cast<size_t>(k)] = c->aln_zero_host[static_cast<size_t>(src)];
+        perm[static_cast<size_t>(k)] = ident ? src : c->lg_perm[static_cast<size_t>(src)];
+      } else {
+        zero[static_cast<size_t>(k)] = r->iv_thr[~src] == FSLR_THR_ZERO_ALN;
+        perm[static_cast<size_t>(k)] = static_cast<int>(ni) + plan->b_perm[~src];
+      }
+    }
+    c->aln_zero_host.swap(zero);
+    c->lg_perm.swap(perm);
+    c->lg_n_real = n_real + m_real;
+    c->lg_max_len = plan->max_len;
+    c->lg_set = true;
+    c->lg_n_edges = 0;
+  }
   c->n = need_n;
   c->ni = need_ni;
   c->ni_idx = need_ni;
@@ -400,11 +541,15 @@ int fslr_append_reads(fslr_ctx* c, const fslr_reads* r) {
   return FSLR_OK;
 }
 
+extern "C" {
+
+int fslr_append_reads(fslr_ctx* c, const fslr_reads* r) { return append_core(c, r, nullptr, "fslr_append_reads"); }
+
 int fslr_append_timings(fslr_ctx* c, float* ms) {
   if (!c || !ms) return FSLR_ERR_INVALID;
   AppendWork* w = c->apw;
   if (!w || !w->timed)
-    return fail(c, FSLR_ERR_STATE, "fslr_append_timings: no profiled fslr_append_reads (fslr_set_profiling 1 or 2)");
+    return fail(c, FSLR_ERR_STATE, "fslr_append_timings: no profiled fslr_append_reads / fslr_append_reads_any (fslr_set_profiling 1 or 2)");
   for (int t = 0; t < 4; ++t) ms[t] = w->ms[t];
   return FSLR_OK;
 }

@@ -2730,6 +2730,7 @@ extern "C" int fslr_long_pairs_shard(fslr_ctx* c, const fslr_params* p, int32_t 
   if (!c || !p || !n_edges || n_shards < 1 || shard < 0 || shard >= n_shards) return FSLR_ERR_INVALID;
   *n_edges = 0;
   if (!c->lg_set) return fail(c, FSLR_ERR_STATE, "fslr_set_long_reads first");
+  if (c->lg_n_umax < c->lg_max_len) return fail(c, FSLR_ERR_INVALID, "umax must cover I up to the longest read");
   if (!c->index_built || c->filter_active) return fail(c, FSLR_ERR_STATE, "fslr_build_index (every chromosome) first");
   HIP_TRY(c, hipSetDevice(c->device));
   hipStream_t s = c->stream;

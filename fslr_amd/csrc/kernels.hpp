@@ -290,6 +290,10 @@ struct UploadArgs {
   // fslr_append_reads packs a batch behind the resident reads: its read r has rank rank_base + r and its
   // intervals follow at CSR offset off_base (0, 0: fslr_set_reads)
   int rank_base = 0, off_base = 0;
+  // fslr_append_reads_any packs a batch of virtual reads whose further chunks land behind the resident ones:
+  // a batch read r >= split has rank rank_base2 + r and CSR offset off_base2 + off[r] (no split: every read
+  // takes rank_base / off_base, today's bytes)
+  int split = 0x7fffffff, rank_base2 = 0, off_base2 = 0;
   // outputs
   int4* iv;
   int4* rmeta;

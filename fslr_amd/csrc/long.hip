@@ -408,6 +408,8 @@ static int long_evaluate(fslr_ctx* c, const void* entries, int64_t n, void* shor
 extern "C" int fslr_long_query(fslr_ctx* c, const fslr_params* p, int64_t* n_long_edges) {
   if (!c || !p || !n_long_edges) return FSLR_ERR_INVALID;
   if (!c->lg_set) return fail(c, FSLR_ERR_STATE, "fslr_set_long_reads first");
+  // (fslr_append_reads_any leaves the cutoffs alone: a longer read needs fslr_set_long_cutoffs again)
+  if (c->lg_n_umax < c->lg_max_len) return fail(c, FSLR_ERR_INVALID, "umax must cover I up to the longest read");
   HIP_TRY(c, hipSetDevice(c->device));
   // 1. every match entry of the virtual index (one destination), into a context-owned buffer
   int64_t cnt = 0;

@@ -324,12 +324,7 @@ int ensure(fslr_ctx* c, T** p, int64_t* cap, int64_t need, int64_t mult = 1) {
   return FSLR_OK;
 }
 
-// once memory is there nothing but the device can fail; what is then half written is not a set of reads
-int broken(fslr_ctx* c, int rc) {
-  c->reads_set = false;
-  c->index_built = false;
-  return rc;
-}
+int broken(fslr_ctx* c, int rc) { return reads_broken(c, rc); }
 
 #define RM_TRY(ctx, expr)                                                                                     \
   do {                                                                                                        \
@@ -340,32 +335,43 @@ int broken(fslr_ctx* c, int rc) {
 
 }  // namespace
 
-extern "C" {
-
-int fslr_remove_reads(fslr_ctx* c, int64_t n_in, const uint8_t* keep, int32_t* new_rank) {
-  if (!c) return FSLR_ERR_INVALID;
-  if (!c->reads_set) return fail(c, FSLR_ERR_STATE, "fslr_remove_reads: no reads set (fslr_set_reads first)");
+// the states neither removal takes, each named; virt: virtual reads are fine (fslr_remove_reads_any)
+int fslr::remove_state(fslr_ctx* c, const std::string& who, bool virt) {
+  if (!c->reads_set) return fail(c, FSLR_ERR_STATE, who + ": no reads set (fslr_set_reads first)");
   if (c->rows_set)
-    return fail(c, FSLR_ERR_STATE, "fslr_remove_reads: the reads were made from rows (fslr_set_reads_rows), which it does not compact");
-  if (c->lg_set || !c->lg_perm.empty())
-    return fail(c, FSLR_ERR_STATE, "fslr_remove_reads: the context holds virtual reads (fslr_set_reads_any / fslr_set_long_reads: "
+    return fail(c, FSLR_ERR_STATE, who + ": the reads were made from rows (fslr_set_reads_rows), which it does not compact");
+  if (!virt && (c->lg_set || !c->lg_perm.empty()))
+    return fail(c, FSLR_ERR_STATE, who + ": the context holds virtual reads (fslr_set_reads_any / fslr_set_long_reads: "
                                    "reads of more than " + std::to_string(FSLR_MAX_L) + " intervals), which it does not compact");
+  if (virt && c->lg_set && c->lg_perm.empty())
+    return fail(c, FSLR_ERR_STATE, who + ": the virtual reads were made by the caller (fslr_set_long_reads), not by "
+                                   "fslr_set_reads_any: their real CSR is not known here");
   if (!c->have_data_pos)
-    return fail(c, FSLR_ERR_STATE, "fslr_remove_reads: the reads were set without iv_data_pos (no start-sorted data list to compact)");
-  if (c->n_shards > 1) return fail(c, FSLR_ERR_STATE, "fslr_remove_reads: n_shards > 1 (fslr_set_shard): multi-GPU contexts do not remove");
+    return fail(c, FSLR_ERR_STATE, who + ": the reads were set without iv_data_pos (no start-sorted data list to compact)");
+  if (c->n_shards > 1) return fail(c, FSLR_ERR_STATE, who + ": n_shards > 1 (fslr_set_shard): multi-GPU contexts do not remove");
   if (c->filter_active || c->pf_on)
-    return fail(c, FSLR_ERR_STATE, "fslr_remove_reads: a chromosome or position filter is active");
+    return fail(c, FSLR_ERR_STATE, who + ": a chromosome or position filter is active");
+  return FSLR_OK;
+}
+
+// virt: fslr_remove_reads_any's compaction of the virtual reads (keep, n_in and the map are over them; the map's
+// first n_rank entries, the real reads', go back to the caller)
+int fslr::remove_core(fslr_ctx* c, int64_t n_in, const uint8_t* keep, int32_t* new_rank, int64_t n_rank, const char* who_c,
+                      bool virt) {
+  if (!c) return FSLR_ERR_INVALID;
+  const std::string who(who_c);
+  if (int rc = remove_state(c, who, virt)) return rc;
   const int64_t n = c->n, ni = c->ni;
   if (n_in != n)
-    return fail(c, FSLR_ERR_INVALID, "fslr_remove_reads: n = " + std::to_string(n_in) + " but the context holds " +
+    return fail(c, FSLR_ERR_INVALID, who + ": n = " + std::to_string(n_in) + " but the context holds " +
                                          std::to_string(n) + " reads");
-  if (!keep) return fail(c, FSLR_ERR_INVALID, "fslr_remove_reads: keep is NULL");
+  if (!keep) return fail(c, FSLR_ERR_INVALID, who + ": keep is NULL");
   int64_t n_kept = 0;
   for (int64_t r = 0; r < n; ++r) n_kept += keep[r] != 0;
-  if (n_kept == 0) return fail(c, FSLR_ERR_INVALID, "fslr_remove_reads: would leave no reads");
+  if (n_kept == 0) return fail(c, FSLR_ERR_INVALID, who + ": would leave no reads");
   if (n_kept == n) {                             // nothing to remove: no generation moves
     if (new_rank)
-      for (int64_t r = 0; r < n; ++r) new_rank[r] = static_cast<int32_t>(r);
+      for (int64_t r = 0; r < n_rank; ++r) new_rank[r] = static_cast<int32_t>(r);
     return FSLR_OK;
   }
   HIP_TRY(c, hipSetDevice(c->device));
@@ -453,11 +459,11 @@ int fslr_remove_reads(fslr_ctx* c, int64_t n_in, const uint8_t* keep, int32_t* n
   int stat[4] = {0, 0, 0, 0};
   RM_TRY(c, hipMemcpyAsync(counts.data(), w->cnt, counts.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
   RM_TRY(c, hipMemcpyAsync(stat, w->stat, sizeof(stat), hipMemcpyDeviceToHost, st));
-  if (new_rank) RM_TRY(c, hipMemcpyAsync(new_rank, w->new_rank, static_cast<size_t>(n) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  if (new_rank) RM_TRY(c, hipMemcpyAsync(new_rank, w->new_rank, static_cast<size_t>(n_rank) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
   RM_TRY(c, hipStreamSynchronize(st));
   const int64_t ni_kept = stat[1];
   if (stat[0] != n_kept || (d_tiles && stat[2] != stat[1]) || ni_kept < n_kept || ni_kept > ni)
-    return broken(c, fail(c, FSLR_ERR_HIP, "fslr_remove_reads: the two orders disagree (" + std::to_string(stat[0]) + " reads, " +
+    return broken(c, fail(c, FSLR_ERR_HIP, who + ": the two orders disagree (" + std::to_string(stat[0]) + " reads, " +
                                                std::to_string(stat[1]) + " / " + std::to_string(stat[2]) + " intervals kept)"));
   // chromosome ranges of the (chrom, start)-sorted index from the kept counts, as fslr_set_reads makes them
   std::vector<int2> cr(counts.size(), make_int2(0, 0));
@@ -504,11 +510,29 @@ int fslr_remove_reads(fslr_ctx* c, int64_t n_in, const uint8_t* keep, int32_t* n
   return FSLR_OK;
 }
 
+const int* fslr::remove_rank_map(fslr_ctx* c) { return c->rmw ? c->rmw->new_rank : nullptr; }
+
+int fslr::remove_extend_timings(fslr_ctx* c) {
+  RemoveWork* w = c->rmw;
+  if (!w || !w->timed) return FSLR_OK;
+  HIP_TRY(c, hipEventRecord(w->ev[3], c->stream));
+  HIP_TRY(c, hipEventSynchronize(w->ev[3]));
+  HIP_TRY(c, hipEventElapsedTime(&w->ms[2], w->ev[2], w->ev[3]));
+  HIP_TRY(c, hipEventElapsedTime(&w->ms[3], w->ev[0], w->ev[3]));
+  return FSLR_OK;
+}
+
+extern "C" {
+
+int fslr_remove_reads(fslr_ctx* c, int64_t n, const uint8_t* keep, int32_t* new_rank) {
+  return remove_core(c, n, keep, new_rank, n, "fslr_remove_reads", false);
+}
+
 int fslr_remove_timings(fslr_ctx* c, float* ms) {
   if (!c || !ms) return FSLR_ERR_INVALID;
   RemoveWork* w = c->rmw;
   if (!w || !w->timed)
-    return fail(c, FSLR_ERR_STATE, "fslr_remove_timings: no profiled fslr_remove_reads (fslr_set_profiling 1 or 2)");
+    return fail(c, FSLR_ERR_STATE, "fslr_remove_timings: no profiled fslr_remove_reads / fslr_remove_reads_any (fslr_set_profiling 1 or 2)");
   for (int t = 0; t < 4; ++t) ms[t] = w->ms[t];
   return FSLR_OK;
 }

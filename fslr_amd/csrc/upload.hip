@@ -50,13 +50,13 @@ __global__ __launch_bounds__(256) void k_up_chist(const int* __restrict__ chrom,
 // per read: {CSR offset, L | zero-aln flag << 16, qlen2, n_alignments} and its 1-byte length (read_off
 // was validated on the host: every read has 1 .. FSLR_MAX_L intervals inside [0, ni))
 __global__ void k_up_reads(const int* __restrict__ off, const int* __restrict__ qlen2, const int* __restrict__ nal,
-                           const int* __restrict__ thr, int n, int off_base, int4* __restrict__ rmeta,
-                           unsigned char* __restrict__ rlen8) {
+                           const int* __restrict__ thr, int n, int off_base, int split, int off_base2,
+                           int4* __restrict__ rmeta, unsigned char* __restrict__ rlen8) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const int o = off[i], len = off[i + 1] - o;
     int flags = 0;
     for (int k = o; k < o + len; ++k) flags |= thr[k] == FSLR_THR_ZERO_ALN;
-    rmeta[i] = make_int4(o + off_base, len | (flags << 16), qlen2[i], nal[i]);
+    rmeta[i] = make_int4(o + (i < split ? off_base : off_base2), len | (flags << 16), qlen2[i], nal[i]);
     rlen8[i] = static_cast<unsigned char>(len);
   }
 }
@@ -85,8 +85,8 @@ __global__ void k_up_sorted(const int* __restrict__ inv, const int* __restrict__
 // owning read's gate word (kernels.hpp idx_gate; the reference's IntervalItem carries qlen2 and
 // n_alignments, cluster.py:10-11).  One thread per read, its intervals in CSR order.
 __global__ void k_up_data(const int* __restrict__ off, const int* __restrict__ dp, const int4* __restrict__ iv,
-                          const int4* __restrict__ rmeta, int n, int ni, int rank_base, unsigned* __restrict__ dch,
-                          int4* __restrict__ drc, int2* __restrict__ dgt) {
+                          const int4* __restrict__ rmeta, int n, int ni, int rank_base, int split, int rank_base2,
+                          unsigned* __restrict__ dch, int4* __restrict__ drc, int2* __restrict__ dgt) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const int4 m = rmeta[i];
     const int2 gate = make_int2(m.z, (m.w & 0xFFFFFF) | ((m.y & 0x7F) << 24) | (((m.y >> 16) & 1) << 31));
@@ -96,7 +96,7 @@ __global__ void k_up_data(const int* __restrict__ off, const int* __restrict__ d
       if (d < 0 || d >= ni) continue;                  // flagged by k_up_inv; nothing written out of range
       const int4 v = iv[k];
       dch[d] = static_cast<unsigned>(v.x);
-      drc[d] = make_int4(v.y, v.z, v.w, ((rank_base + i) << 6) | (k - o));
+      drc[d] = make_int4(v.y, v.z, v.w, (((i < split ? rank_base : rank_base2) + i) << 6) | (k - o));
       dgt[d] = gate;
     }
   }
@@ -114,13 +114,15 @@ hipError_t launch_upload_pack(const UploadArgs& a, hipStream_t s) {
     k_up_chist<<<std::min(grid_for(a.ni), 1024), 256, 0, s>>>(a.chrom, a.ni, a.n_chroms, a.chrom_cnt);
   }
   if (a.reads_ok && a.n > 0)
-    k_up_reads<<<grid_for(a.n), 256, 0, s>>>(a.off, a.qlen2, a.nal, a.thr, a.n, a.off_base, a.rmeta, a.rlen8);
+    k_up_reads<<<grid_for(a.n), 256, 0, s>>>(a.off, a.qlen2, a.nal, a.thr, a.n, a.off_base, a.split, a.off_base2, a.rmeta,
+                                            a.rlen8);
   if (a.dp && a.ni > 0) {
     k_up_fill<<<grid_for(a.ni), 256, 0, s>>>(a.inv, a.ni, -1);
     k_up_inv<<<grid_for(a.ni), 256, 0, s>>>(a.dp, a.ni, a.inv, a.err);
     k_up_sorted<<<grid_for(a.ni), 256, 0, s>>>(a.inv, a.start, a.ni, a.err);
     if (a.reads_ok && a.n > 0)
-      k_up_data<<<grid_for(a.n), 256, 0, s>>>(a.off, a.dp, a.iv, a.rmeta, a.n, a.ni, a.rank_base, a.dch, a.drc, a.dgt);
+      k_up_data<<<grid_for(a.n), 256, 0, s>>>(a.off, a.dp, a.iv, a.rmeta, a.n, a.ni, a.rank_base, a.split, a.rank_base2,
+                                             a.dch, a.drc, a.dgt);
   }
   return hipGetLastError();
 }

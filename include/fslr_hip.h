@@ -870,6 +870,48 @@ int  fslr_append_timings(fslr_ctx *ctx, float *ms);
 int  fslr_remove_reads(fslr_ctx *ctx, int64_t n, const uint8_t *keep, int32_t *new_rank);
 int  fslr_remove_timings(fslr_ctx *ctx, float *ms);
 
+/* ---- Appending and removing reads of any length -------------------------------------
+ * fslr_append_reads_any and fslr_remove_reads_any are fslr_append_reads and fslr_remove_reads for reads of
+ * 1..FSLR_MAX_ANY_L intervals and for a context that holds virtual reads made by fslr_set_reads_any.
+ *
+ * fslr_append_reads_any: `reads` is a REAL CSR (a read's whole list, not chunks) in the resident dense
+ * chromosome ids, thresholds folded and in real interval order, iv_data_pos REQUIRED (the batch's own
+ * start-sorted order), exactly as fslr_append_reads takes it.  Afterwards the context is the one
+ * fslr_set_reads_any of the union leaves (the resident real reads in their rank order, then the batch), byte
+ * for byte on every resident buffer fslr_append_reads names and on the virtual-read maps (vreal, vbase, rlen,
+ * off2 of the long reads, n_real, the longest read, the host's virtual -> real interval map).  With n resident
+ * real reads, V resident virtual reads and m batch reads: resident virtual reads v < n keep their rank, the
+ * batch's first chunks take [n, n + m), resident further chunks v >= n become v + m, the batch's further chunks
+ * follow; the CSR rows follow the same four groups in that order, and the `data` list is fslr_append_reads'
+ * stable merge with the tags in the new numbering.  A context without virtual reads plus a batch without a
+ * read of more than FSLR_MAX_L intervals takes fslr_append_reads' path and leaves its bytes; with such a read
+ * the context becomes a virtual one.  The long-pair cutoff table is left alone: fslr_set_long_cutoffs must
+ * cover the longest read again before the next fslr_long_query / fslr_long_pairs, which otherwise refuse
+ * ("umax must cover I up to the longest read"; a context that just became virtual holds the zero placeholder
+ * of a fresh upload).
+ * Cost: H2D of the batch's columns and maps only; the split into chunks is a host pass over the batch; the
+ * relocation of the resident rows, reads and maps runs on the device (never in place: into index-build
+ * scratch and freshly allocated maps, swapped in).  The host's per-interval marks and its virtual -> real
+ * interval map (4 B + 1 B per interval) are rewritten by one host pass.  The first _any call after an upload
+ * reads the real reads' lengths back once (4 B per real read; 1 B on a plain context).
+ *
+ * fslr_remove_reads_any: keep and new_rank are over the REAL ranks, n must equal the real read count.  A
+ * removed read loses all its chunks.  Afterwards the context is fslr_set_reads_any of the surviving real CSR,
+ * byte for byte; once no read of more than FSLR_MAX_L intervals survives it is a plain context (the bytes of
+ * fslr_set_reads, the threshold mode and the aln_size == 0 mark recomputed as fslr_remove_reads does).  On a
+ * context without virtual reads it is fslr_remove_reads.
+ *
+ * Both: atomic as the short calls are (a refused or out-of-memory call leaves the reads, a built index and the
+ * saved batches untouched; nothing resident is written before validation has passed and everything is
+ * allocated; a device failure past that point leaves no reads set); the same invalidations; the same
+ * FSLR_ERR_STATE list without the virtual-reads line (no reads set, rows-made reads, no iv_data_pos, n_shards
+ * > 1, an active filter), plus: virtual reads a caller made with fslr_set_long_reads (their real CSR is not
+ * known to the library) are FSLR_ERR_STATE, and a batch read of more than FSLR_MAX_ANY_L intervals is
+ * FSLR_ERR_INVALID, named.  fslr_append_timings / fslr_remove_timings report the last call of either kind
+ * (the relocation counts into the append's merge phase, the removal's map kernels into its compaction phase). */
+int  fslr_append_reads_any(fslr_ctx *ctx, const fslr_reads *reads);
+int  fslr_remove_reads_any(fslr_ctx *ctx, int64_t n_real, const uint8_t *keep, int32_t *new_rank);
+
 /* Device-side views for collectives (e.g. RCCL all_gather of labels). */
 int  fslr_labels_device_ptr(fslr_ctx *ctx, void **dptr);
 /* Copy the [n_reads] labels into a caller-owned device buffer on this device (async, ctx stream). */
