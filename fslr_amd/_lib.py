@@ -50,7 +50,8 @@ EXPORTED = ['fslr_abi_version', 'fslr_last_error', 'fslr_ctx_create', 'fslr_ctx_
             'fslr_choose_representatives', 'fslr_cluster_timings',
             'fslr_match_reads', 'fslr_match_rows', 'fslr_match_timings', 'fslr_score_pairs_any',
             'fslr_match_reads_any', 'fslr_match_rows_any', 'fslr_append_reads', 'fslr_append_timings',
-            'fslr_remove_reads', 'fslr_remove_timings', 'fslr_append_reads_any', 'fslr_remove_reads_any']
+            'fslr_remove_reads', 'fslr_remove_timings', 'fslr_append_reads_any', 'fslr_remove_reads_any',
+            'fslr_pair_matching', 'fslr_pair_matching_any', 'fslr_pair_matching_timings']
 # fslr_score_pairs' flag bits (include/fslr_hip.h)
 SCORE_GATE, SCORE_EDGE, SCORE_ZD_GATE, SCORE_ZD_OVERLAP = 1, 2, 4, 8
 # fslr_coverage_*: keys per tile of the sorted arrays, queries per chunk (include/fslr_hip.h)
@@ -241,6 +242,11 @@ def load(path: str = LIB_PATH):
         'fslr_score_pairs': (ctypes.c_int, [vp, ctypes.POINTER(Params), i64, vp, vp, vp, vp, vp]),
         'fslr_score_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         'fslr_score_pairs_any': (ctypes.c_int, [vp, ctypes.POINTER(Params), vp, i32, i64, vp, vp, vp, vp, vp]),
+        'fslr_pair_matching': (ctypes.c_int, [vp, ctypes.POINTER(Params), i64, vp, vp, vp, vp, vp, vp, vp, vp, i64,
+                                              ctypes.POINTER(ctypes.c_int64)]),
+        'fslr_pair_matching_any': (ctypes.c_int, [vp, ctypes.POINTER(Params), vp, i32, i64, vp, vp, vp, vp, vp, vp, vp,
+                                                  vp, i64, ctypes.POINTER(ctypes.c_int64)]),
+        'fslr_pair_matching_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         'fslr_match_reads': (ctypes.c_int, [vp, ctypes.POINTER(Params), ctypes.POINTER(MatchQueries), ctypes.c_uint32,
                                             vp, vp, vp, ctypes.POINTER(ctypes.c_int64)]),
         'fslr_match_rows': (ctypes.c_int, [vp, vp, vp, vp, vp, i64]),
@@ -1055,6 +1061,60 @@ class Context:
         """HIP-event times (ms) of the last score_pairs (profiling contexts), summed over its chunks."""
         ms = (ctypes.c_float * 3)()
         self._check(self._L.fslr_score_timings(self._h, ms))
+        return dict(zip(('upload', 'kernel', 'download'), (float(x) for x in ms)))
+
+    # -- the matching of scored pairs (fslr_hip.h fslr_pair_matching) ---------------------------------
+    def pair_matching(self, a, b, qlen_cut, nal_cut, pass_table):
+        """score_pairs and, per pair, which interval of list1 took which interval of list2 in the first-fit
+        (fslr_pair_matching): ``(I, U, flags, offsets int64[n + 1], i int32[total], j int32[total])``; pair
+        k's rows are ``offsets[k]:offsets[k + 1]``, ``i`` ascending, I[k] of them (none for a pair flagged
+        SCORE_ZD_OVERLAP)."""
+        return self._pair_matching(False, a, b, qlen_cut, nal_cut, pass_table, None)
+
+    def pair_matching_any(self, a, b, qlen_cut, nal_cut, pass_table, umax=None):
+        """pair_matching for reads of any length (fslr_pair_matching_any): real read ranks, whole real
+        lists, ``umax`` as score_pairs_any takes it."""
+        return self._pair_matching(True, a, b, qlen_cut, nal_cut, pass_table, umax)
+
+    def _pair_matching(self, any_length, a, b, qlen_cut, nal_cut, pass_table, umax):
+        a, b = (np.ascontiguousarray(x, dtype=np.int32) for x in (a, b))
+        if not (a.ndim == 1 and a.shape == b.shape):
+            raise ValueError('a and b must be one-dimensional and of one length')
+        um = None
+        if umax is not None:
+            um = np.ascontiguousarray(umax, dtype=np.int32)
+            if um.ndim != 1:
+                raise ValueError('umax must be one-dimensional')
+        p = self._params(qlen_cut, nal_cut, pass_table, 0)
+        n = int(a.size)
+        I, U, flags = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.uint8)
+        off = np.zeros(n + 1, np.int64)
+        # rows: at most min(L1, L2) per pair, from the host's copy of the reads' lengths.  Where the reads were
+        # made on the device (set_reads_rows) there is no such copy: a count-only call sizes the arrays
+        L = np.asarray(getattr(self, '_read_len', np.zeros(0)), np.int64)
+        # (a copy that is out of date costs a second call, never a wrong answer: a short capacity is retried)
+        known = n > 0 and a.min() >= 0 and b.min() >= 0 and max(a.max(), b.max()) < L.size
+        cap = int(np.minimum(L[a], L[b]).sum()) if known else 0
+        total = ctypes.c_int64(0)
+        while True:
+            row, col = np.empty(cap, np.int32), np.empty(cap, np.int32)
+            tail = (_ptr(a), _ptr(b), _ptr(I), _ptr(U), _ptr(flags), _ptr(off), _ptr(row) if cap else None,
+                    _ptr(col) if cap else None, cap, ctypes.byref(total))
+            if any_length:
+                rc = self._L.fslr_pair_matching_any(self._h, ctypes.byref(p), _ptr(um) if um is not None else None,
+                                                    int(um.size) if um is not None else 0, n, *tail)
+            else:
+                rc = self._L.fslr_pair_matching(self._h, ctypes.byref(p), n, *tail)
+            if total.value <= cap:
+                break
+            cap = int(total.value)
+        self._check(rc)
+        return I, U, flags, off, row[:total.value], col[:total.value]
+
+    def pair_matching_timings(self) -> dict:
+        """HIP-event times (ms) of the last pair_matching (profiling contexts), summed over its chunks."""
+        ms = (ctypes.c_float * 3)()
+        self._check(self._L.fslr_pair_matching_timings(self._h, ms))
         return dict(zip(('upload', 'kernel', 'download'), (float(x) for x in ms)))
 
     # -- new reads against the resident index (fslr_hip.h fslr_match_reads / fslr_match_rows) --------

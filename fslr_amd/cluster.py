@@ -50,6 +50,7 @@ __all__ = ['IntervalItem', 'keep_fillings', 'rename_chromosomes', 'chrom_to_str'
            'get_chromosome_lengths', 'query_interval_trees', 'get_subgraphs', 'choose_alignment',
            'ClusterGraph', 'DeviceIntervalIndex', 'ChromosomeView', 'MultiGpuIndex', 'EdgeCapWarning',
            'calculate_overlap', 'overall_jaccard_similarity', 'different_lengths_or_alignments', 'PairScores',
+           'PairMatching',
            'device_coverage', 'DeviceCoverage', 'ClusterTable', 'cluster_table']
 
 
@@ -421,11 +422,13 @@ class PairScores:
     ranks), ``I``, ``U`` (overall_jaccard_similarity's intersection and union), ``jaccard`` (float64 I / U,
     0.0 where U == 0), ``gate`` (different_lengths_or_alignments is False), ``edge`` (the pair loop would
     add the edge, cluster.py:216-221), ``zero_division`` (the reference raises for this pair: I = U = 0
-    where calculate_overlap does) and the raw ``flags`` (fslr_hip.h FSLR_SCORE_*)."""
+    where calculate_overlap does) and the raw ``flags`` (fslr_hip.h FSLR_SCORE_*).  ``matching`` is None
+    unless the pairs were scored with ``matching=True`` (a PairMatching)."""
 
-    def __init__(self, a, b, I, U, flags, qnames_by_rank):
+    def __init__(self, a, b, I, U, flags, qnames_by_rank, matching=None):
         self.a, self.b, self.I, self.U, self.flags = a, b, I, U, flags
         self.qnames_by_rank = qnames_by_rank
+        self.matching = matching
         self.jaccard = np.divide(I, U, out=np.zeros(I.shape, np.float64), where=U != 0)
         self.gate = (flags & SCORE_GATE) != 0
         self.edge = (flags & SCORE_EDGE) != 0
@@ -440,6 +443,37 @@ class PairScores:
         return pd.DataFrame({'query1': q[self.a] if n else np.zeros(0, object),
                              'query2': q[self.b] if n else np.zeros(0, object),
                              'jaccard_similarity': self.jaccard, 'n_i': self.I, 'gate': self.gate, 'edge': self.edge})
+
+
+class PairMatching:
+    """Which interval of query1's list took which interval of query2's in the first-fit (fslr_pair_matching):
+    pair k's rows are ``offsets[k]:offsets[k + 1]`` of ``i`` (index into query1's list, ascending) and ``j``
+    (index into query2's list); I[k] rows, none for a pair whose overlap raised ZeroDivisionError."""
+
+    def __init__(self, scores, offsets, i, j, intervals):
+        self.offsets, self.i, self.j = offsets, i, j
+        self._scores, self._intervals = scores, intervals
+
+    def __len__(self):
+        return int(self.i.shape[0])
+
+    def pair_of_row(self) -> np.ndarray:
+        """The input pair (its position) of every row."""
+        return np.repeat(np.arange(self.offsets.shape[0] - 1, dtype=np.int64), np.diff(self.offsets))
+
+    def to_frame(self):
+        """One row per matched interval pair: ``query1``, ``query2``, ``i``, ``j`` and both intervals'
+        ``chrom``, ``start``, ``end`` (the chromosome values the index was built with)."""
+        s, k = self._scores, self.pair_of_row()
+        q = s.qnames_by_rank
+        n = len(self)
+        chrom, start, end, read_off = self._intervals
+        p1 = read_off[s.a[k]] + self.i
+        p2 = read_off[s.b[k]] + self.j
+        return pd.DataFrame({'query1': q[s.a[k]] if n else np.zeros(0, object),
+                             'query2': q[s.b[k]] if n else np.zeros(0, object), 'i': self.i, 'j': self.j,
+                             'chrom1': chrom[p1], 'start1': start[p1], 'end1': end[p1],
+                             'chrom2': chrom[p2], 'start2': start[p2], 'end2': end[p2]})
 
 
 class ReadMatches:
@@ -779,21 +813,23 @@ class DeviceIntervalIndex:
             raise KeyError(f'{e.args[0]!r} is not a read of this index') from None
 
     def score_pairs(self, query1, query2, overlap_cutoff, jaccard_threshold, qlen_diff, diff,
-                    raise_zero_division=False) -> PairScores:
+                    raise_zero_division=False, matching=False) -> PairScores:
         """What the reference's pair loop computes for the ordered read pairs ``(query1[k], query2[k])``
         (integer read ranks, or qnames), whether or not a query would reach them: list1 = query1's
         intervals, list2 = query2's.  One batched device call (fslr_score_pairs); the query state of the
         index (edges, labels) is left alone.  ZeroDivisionError is flagged per pair
-        (``PairScores.zero_division``); ``raise_zero_division`` raises it for the first flagged pair."""
+        (``PairScores.zero_division``); ``raise_zero_division`` raises it for the first flagged pair.
+        ``matching=True`` also returns which interval took which (fslr_pair_matching) as
+        ``PairScores.matching``, a PairMatching."""
         min(jaccard_threshold)                              # cluster.py:188 raises on an empty list
         if self.long is not None:
             raise NotImplementedError(f'score_pairs does not take an index with reads of more than {FSLR_MAX_L} '
                                       f'intervals')
         return self._score_pairs(query1, query2, overlap_cutoff, jaccard_threshold, qlen_diff, diff,
-                                 raise_zero_division, False)
+                                 raise_zero_division, False, matching)
 
     def score_pairs_any(self, query1, query2, overlap_cutoff, jaccard_threshold, qlen_diff, diff,
-                        raise_zero_division=False) -> PairScores:
+                        raise_zero_division=False, matching=False) -> PairScores:
         """score_pairs on any index, with or without reads of more than FSLR_MAX_L intervals (up to 4096, the
         index's limit): the ranks are the reads' own, a read's list is its whole list, I and U are unclamped
         and the edge rule beyond the pass table is ``umax_table(jaccard_threshold, longest read)``
@@ -801,10 +837,10 @@ class DeviceIntervalIndex:
         if not len(jaccard_threshold):
             raise ValueError('jaccard_threshold is empty (cluster.py:188 takes its min())')
         return self._score_pairs(query1, query2, overlap_cutoff, jaccard_threshold, qlen_diff, diff,
-                                 raise_zero_division, True)
+                                 raise_zero_division, True, matching)
 
     def _score_pairs(self, query1, query2, overlap_cutoff, jaccard_threshold, qlen_diff, diff, raise_zero_division,
-                     any_length):
+                     any_length, matching=False):
         a, b = self._ranks(query1), self._ranks(query2)
         if a.shape != b.shape:
             raise ValueError('query1 and query2 must be of one length')
@@ -816,18 +852,29 @@ class DeviceIntervalIndex:
         elif self.__dict__.get('_thr_key') != (float(overlap_cutoff), getattr(ctx, 'thr_gen', 0)):
             ctx.set_thresholds(fold_overlap_threshold(self.csr.iv_aln, overlap_cutoff))
             self._thr_key = (float(overlap_cutoff), ctx.thr_gen)
+        rows = None
         if any_length:
             umax = umax_table(jaccard_threshold, int(self.long.max())) if self.long is not None else None
-            I, U, flags = ctx.score_pairs_any(a, b, 1 - qlen_diff, 1 - diff, pass_table(jaccard_threshold), umax)
+            call = ctx.pair_matching_any if matching else ctx.score_pairs_any
+            I, U, flags, *rows = call(a, b, 1 - qlen_diff, 1 - diff, pass_table(jaccard_threshold), umax)
         else:
-            I, U, flags = ctx.score_pairs(a, b, 1 - qlen_diff, 1 - diff, pass_table(jaccard_threshold))
+            call = ctx.pair_matching if matching else ctx.score_pairs
+            I, U, flags, *rows = call(a, b, 1 - qlen_diff, 1 - diff, pass_table(jaccard_threshold))
         qn = self.data.qnames[self.csr.read_qcode]
         if raise_zero_division:
             bad = np.flatnonzero(flags & (SCORE_ZD_GATE | SCORE_ZD_OVERLAP))
             if bad.size:
                 k = int(bad[0])
                 raise ZeroDivisionError(f'division by zero (pair {k}: {qn[a[k]]!r}, {qn[b[k]]!r})')
-        return PairScores(a, b, I, U, flags, qn)
+        scores = PairScores(a, b, I, U, flags, qn)
+        if matching:
+            # the intervals in CSR order, chromosomes as the caller's values (data positions of the `data` list)
+            dp = np.asarray(self.csr.data_pos, np.int64)
+            d = self.data
+            cols = (np.asarray(d.chrom)[dp], np.asarray(d.start)[dp], np.asarray(d.end)[dp],
+                    np.asarray(self.csr.read_off, np.int64))
+            scores.matching = PairMatching(scores, *rows, cols)
+        return scores
 
     # -- new reads against the resident index (cluster.py:197-222 with an external list1) -----------
     _EMIT = {'edges': SCORE_EDGE, 'gated': SCORE_GATE, 'all': 0}

@@ -227,6 +227,7 @@ void fslr_ctx_destroy(fslr_ctx* c) {
   fslr_cap_free(c);
   fslr_search_free(c);
   fslr_score_free(c);
+  fslr_pair_matching_free(c);
   fslr_coverage_free(c);
   fslr_cluster_free(c);
   fslr_match_free(c);

@@ -179,6 +179,7 @@ struct fslr_ctx {
   struct SearchWork* srw = nullptr;      // fslr_search's buffers and its last batch (search.hip)
   uint64_t index_gen = 0;                // bumped by every fslr_build_index (a saved search batch belongs to one)
   struct ScoreWork* scw = nullptr;       // fslr_score_pairs' scratch and its last call's times (score.hip)
+  struct PairMatchingWork* pmw = nullptr;   // fslr_pair_matching's scratch and its last call's times (matching.hip)
   struct CoverageWork* cvw = nullptr;    // fslr_coverage_build's resident keys, the chunk staging (coverage.hip)
   struct AppendWork* apw = nullptr;      // fslr_append_reads' batch scratch and the second set of data-order buffers (append.hip)
   struct RemoveWork* rmw = nullptr;     // fslr_remove_reads' maps and tile counts (remove.hip)
@@ -234,6 +235,8 @@ void fslr_cap_free(fslr_ctx* c);
 void fslr_search_free(fslr_ctx* c);
 // frees the pair scoring's buffers (score.hip)
 void fslr_score_free(fslr_ctx* c);
+// frees the pair matching's buffers (matching.hip)
+void fslr_pair_matching_free(fslr_ctx* c);
 // frees the resident coverage set and its staging (coverage.hip)
 void fslr_coverage_free(fslr_ctx* c);
 // frees the resident cluster table and its scratch (clusters.hip)

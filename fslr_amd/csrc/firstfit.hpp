@@ -6,12 +6,15 @@
 //   match.hip  k_match_score<kAny>: the same, list1's rows read from LDS
 //   cap.hip    k_cap_eval: lane_fit for two short reads, long_fit for every other slot
 //   query.hip  deferred_kernel: FirstFit::row<64> for a deferred pair
+//   matching.hip  k_pair_matching<kAny, kEmit>: score.hip's groups; the emit pass with the recording variant
+//              (FirstFitT<true>, long_fit with a recorder), which keeps which row took which column
 //
 // List2's columns sit on the lanes of a W-lane group (W in {16, 32, 64}; 64 / W pairs side by side in a
 // wavefront), list1's rows are stepped uniformly over the group: where a row comes from (a broadcast
 // record in score.hip and query.hip, LDS in match.hip) is the caller's.
 #pragma once
 #include <cstdint>
+#include <type_traits>
 
 #include "fslr_hip.h"
 #include "kernels.hpp"
@@ -30,15 +33,27 @@ __device__ __forceinline__ int gate_flags(int q1, int q2, int n1, int n2, double
 }
 
 // the first-fit state of this lane's group: its column is taken, the pair met calculate_overlap's
-// ZeroDivisionError, and the matches so far (zd and I are uniform over the group)
-struct FirstFit {
+// ZeroDivisionError, and the matches so far (zd and I are uniform over the group).
+// kRec (matching.hip): the recording variant.  The lane that wins a row keeps that row's index (ri) and the
+// pair's match count at that moment (ord): in registers, no memory is touched.  Where the rows are stepped in
+// ascending order over one set of columns (the lane groups), ord is the row's position among the pair's
+// matched rows.  FirstFit, the plain state, holds neither (FitNoRec) and compiles as it did before the variant
+// existed.
+struct FitNoRec {};
+struct FitRowRec {
+  int ri = -1, ord = 0;
+};
+template <bool kRec>
+struct FirstFitT : std::conditional_t<kRec, FitRowRec, FitNoRec> {
   bool used = false, zd = false;
   int I = 0;
 
   // one row (chrom, start, end, thr) of list1 against the group's columns (col: this lane holds column
-  // bj of list2); live: the row exists for this group (the wave may step past a shorter list1)
+  // bj of list2); live: the row exists for this group (the wave may step past a shorter list1); i (kRec):
+  // the row's index in list1
   template <int W>
-  __device__ __forceinline__ void row(int c, int si, int ei, int ti, bool live, int4 bj, bool col, int lane) {
+  __device__ __forceinline__ void row(int c, int si, int ei, int ti, bool live, int4 bj, bool col, int lane,
+                                      int i = 0) {
     const int l = lane & (W - 1);
     const int gbase = lane & ~(W - 1);
     // on copies, written back at the end: the step then compiles as it did inside the kernels' loops
@@ -60,12 +75,16 @@ struct FirstFit {
         z = true;                      // the row's walk meets the aln_size == 0 column before any match
       } else {
         u |= l == j;
+        if constexpr (kRec) {
+          if (l == j) this->ri = i, this->ord = n;
+        }
         ++n;
       }
     }
     used = u, zd = z, I = n;
   }
 };
+using FirstFit = FirstFitT<false>;
 
 // The scalar statement of the same rule, by one lane, for two reads of few intervals (LB <= 32: one bit of
 // `used` per column; cap.hip takes it up to 16): rows ascending, the lowest unused column of the row's
@@ -129,8 +148,22 @@ inline void fit_unpack(unsigned v, int32_t* I, int32_t* U, uint8_t* flags) {
 // alone; an earlier row still unmatched when the chunk starts is stepped before it inside the chunk, and a
 // row matched in an earlier chunk never looks at this one.  rows(i) / cols(j): record i of list1 / j of
 // list2 (chrom, start, end, thr).  The matched bits: rows [64 s, 64 s + 64) on lane s, two 32-bit words.
-template <class Rows, class Cols>
-__device__ __forceinline__ void long_fit(int LA, int LB, Rows rows, Cols cols, int lane, int* I_out, bool* zd_out) {
+//
+// rec (matching.hip): what a caller keeps of the matching.  A column is taken at most once, so after a
+// chunk every used lane still holds the row that took its column: rec->chunk(used, row, column) runs once
+// per chunk, outside the row loops, on every lane; rec->done(lo, hi) hands over the matched bits at the end.
+// A row may be matched in a later chunk than a later row was, so the order of the matches is not the order
+// of the rows here: the caller ranks the rows from the matched bits.  Without a recorder (NoFitRec, the
+// default: rec is not looked at) the function compiles as it did before it took one.
+struct NoFitRec {
+  static constexpr bool on = false;
+  __device__ __forceinline__ void chunk(bool, int, int) {}
+  __device__ __forceinline__ void done(unsigned, unsigned) {}
+};
+
+template <class Rows, class Cols, class Rec = NoFitRec>
+__device__ __forceinline__ void long_fit(int LA, int LB, Rows rows, Cols cols, int lane, int* I_out, bool* zd_out,
+                                         Rec* rec = nullptr) {
   unsigned done_lo = 0, done_hi = 0;
   int matched = 0;
   bool zd = false;
@@ -139,7 +172,7 @@ __device__ __forceinline__ void long_fit(int LA, int LB, Rows rows, Cols cols, i
     const bool col = c0 + lane < LB;
     int4 bj = make_int4(-2, 0, 0, 0);
     if (col) bj = cols(c0 + lane);
-    FirstFit ff;                                   // this chunk's columns: used, and the matches made in it
+    FirstFitT<Rec::on> ff;                         // this chunk's columns: used, and the matches made in it
     for (int s = 0; s < nslice && !ff.zd; ++s) {
       const int nr = min(kWave, LA - s * kWave);
       const unsigned long long live = nr == kWave ? ~0ull : (1ull << nr) - 1;
@@ -155,7 +188,8 @@ __device__ __forceinline__ void long_fit(int LA, int LB, Rows rows, Cols cols, i
         const int i = __builtin_ctzll(pend);
         pend &= pend - 1;
         const int before = ff.I;
-        ff.row<kWave>(rdl(ai.x, i), rdl(ai.y, i), rdl(ai.z, i), rdl(ai.w, i), true, bj, col, lane);
+        ff.template row<kWave>(rdl(ai.x, i), rdl(ai.y, i), rdl(ai.z, i), rdl(ai.w, i), true, bj, col, lane,
+                               s * kWave + i);
         if (ff.zd) break;
         if (ff.I != before) got |= 1ull << i;
       }
@@ -166,7 +200,9 @@ __device__ __forceinline__ void long_fit(int LA, int LB, Rows rows, Cols cols, i
       matched += __popcll(got);
     }
     zd = ff.zd;
+    if constexpr (Rec::on) rec->chunk(ff.used, ff.ri, c0 + lane);
   }
+  if constexpr (Rec::on) rec->done(done_lo, done_hi);
   *I_out = matched;
   *zd_out = zd;
 }

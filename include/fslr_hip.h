@@ -794,6 +794,37 @@ int  fslr_match_reads_any(fslr_ctx *ctx, const fslr_params *params, const int32_
                           int32_t *best, int64_t *n_rows);
 int  fslr_match_rows_any(fslr_ctx *ctx, int32_t *partner, int32_t *I, int32_t *U, uint8_t *flags, int64_t capacity);
 
+/* The first-fit matching of scored pairs: fslr_score_pairs' batch, and per pair WHICH
+ * interval of list1 took which interval of list2 in overall_jaccard_similarity's walk (cluster.py:152-161).
+ * a, b, I, U and flags are fslr_score_pairs' (fslr_pair_matching) or fslr_score_pairs_any's
+ * (fslr_pair_matching_any: real ranks, lists of 1..FSLR_MAX_ANY_L intervals, umax), byte for byte what those
+ * calls return for the same batch.
+ *   row_off  [n_pairs + 1] the exclusive scan of I: pair k's rows are row_off[k] .. row_off[k + 1]
+ *   row, col [capacity] per row (i, j): interval i of list1 took interval j of list2; i is strictly ascending
+ *            within a pair and indexes the whole list1, j the whole list2.  A pair has exactly I[k] rows,
+ *            whether or not the gate passes; a pair flagged FSLR_SCORE_ZD_OVERLAP has none.
+ *   n_rows   the total row count (row_off[n_pairs])
+ * capacity >= the sum of min(L1, L2) over the batch can never be short.  When *n_rows > capacity the call
+ * returns FSLR_ERR_INVALID (the message names the count): I, U, flags, row_off and *n_rows are complete, row
+ * and col unspecified.  row == col == NULL with capacity == 0 is a count-only call and returns FSLR_OK.
+ * Errors are fslr_score_pairs' (fslr_score_pairs_any's): no reads set, a rank out of range named by
+ * position with nothing written, virtual reads on the plain call, the umax rules of the _any call.  On a
+ * context without virtual reads the _any call runs the plain call's driver and kernels.  The query state,
+ * the saved search and match batches, the score scratch and every error word are left alone.  The bytes are
+ * the same on every run (no atomic decides a position).  Scratch is bounded: a large batch goes in chunks of
+ * pairs (FSLR_SCORE_CHUNK as in fslr_score_pairs) and a chunk's rows are emitted in sub-ranges that fit the
+ * row scratch, each landing in row / col at the running offset.  Host pointers; syncs.
+ * fslr_pair_matching_timings (fslr_set_profiling 1 or 2): ms[0..2] = upload, kernels (count, scan, emit),
+ * download of the last call of either kind, summed over its chunks. */
+int  fslr_pair_matching(fslr_ctx *ctx, const fslr_params *params, int64_t n_pairs, const int32_t *a, const int32_t *b,
+                        int32_t *I, int32_t *U, uint8_t *flags, int64_t *row_off, int32_t *row, int32_t *col,
+                        int64_t capacity, int64_t *n_rows);
+int  fslr_pair_matching_any(fslr_ctx *ctx, const fslr_params *params, const int32_t *umax, int32_t n_umax,
+                            int64_t n_pairs, const int32_t *a, const int32_t *b, int32_t *I, int32_t *U,
+                            uint8_t *flags, int64_t *row_off, int32_t *row, int32_t *col, int64_t capacity,
+                            int64_t *n_rows);
+int  fslr_pair_matching_timings(fslr_ctx *ctx, float *ms);
+
 /* Append reads to the resident set on the device: what a caller otherwise does by
  * fslr_set_reads of the union.  `reads` describes m new reads with mi intervals exactly as fslr_set_reads
  * takes them: iv_chrom in the resident dense ids, n_chroms >= the resident n_chroms (a larger value adds

@@ -11,6 +11,11 @@ side by side in a wavefront), then the same batch with every pa
 and minimum of the library's HIP-event times (upload, kernel, download) over --repeats calls after
 --warmup, pairs/s of the kernel, the algorithmic bytes (32 B of rmeta + 16 B x (L1 + L2) per pair) and
 the bandwidth they imply over the kernel time.  The two runs must return the same bytes.
+
+--matching adds a third line: fslr_pair_matching on the same batch (mode 'matching': count, scan and emit
+kernels together under 'kernel'), its rows, and its algorithmic bytes: the scoring's, the scan's 12 B per
+pair, the emit pass's second read (32 B + 8 B of offsets + 16 B x (L1 + L2) per pair) and 8 B per row out.
+Its I, U and flags must equal the scoring's.
 """
 import argparse
 import json
@@ -28,7 +33,7 @@ CFG3 = (1_000_000, 16, 11)
 CUTOFFS = (1, 1, 0.66, 0.66, 0.66, 0.5)
 
 
-def run(repeats, warmup):
+def run(repeats, warmup, matching=False):
     from fslr_amd import _lib, synth
     from fslr_amd.prep import fold_overlap_threshold, pass_table
     csr = synth.generate(*CFG3).interval_data().csr()
@@ -69,6 +74,28 @@ def run(repeats, warmup):
             'repeats': repeats, 'warmup': warmup, 'ms_median': med, 'ms_min': {k: float(np.min(v)) for k, v in t.items()},
             'kernel_ms': med['kernel'], 'pairs_per_s': a.size / (med['kernel'] * 1e-3), 'algo_bytes': algo,
             'achieved_GBps': algo / (med['kernel'] * 1e-3) / 1e9}), flush=True)
+    if matching:
+        os.environ['FSLR_SCORE_WIDE'] = '0'
+        t = {k: [] for k in ('upload', 'kernel', 'download', 'wall')}
+        for k in range(warmup + repeats):
+            w0 = time.perf_counter()
+            out = ctx.pair_matching(a, b, 0.96, 0.75, pt)
+            wall = (time.perf_counter() - w0) * 1e3
+            if k >= warmup:
+                for p, v in ctx.pair_matching_timings().items():
+                    t[p].append(v)
+                t['wall'].append(wall)
+        for x, y in zip(out[:3], results[0]):
+            assert np.array_equal(x, y), 'the matching call and the scoring call differ'
+        rows = int(out[4].size)
+        assert rows == int(out[0].sum()) == int(out[3][-1])
+        med = {k: float(np.median(v)) for k, v in t.items()}
+        algo_m = 2 * algo + (4 + 12 + 8) * int(a.size) + 8 * rows
+        print(json.dumps({
+            'case': 'cfg3_edges_plus_random', 'mode': 'matching', 'pairs': int(a.size), 'rows': rows,
+            'repeats': repeats, 'warmup': warmup, 'ms_median': med, 'ms_min': {k: float(np.min(v)) for k, v in t.items()},
+            'kernel_ms': med['kernel'], 'pairs_per_s': a.size / (med['kernel'] * 1e-3), 'algo_bytes': algo_m,
+            'score_algo_bytes': algo + 4 * int(a.size), 'achieved_GBps': algo_m / (med['kernel'] * 1e-3) / 1e9}), flush=True)
     ctx.close()
     for x, y in zip(*results):
         assert np.array_equal(x, y), 'the packed and the 64-lane runs differ'
@@ -80,21 +107,23 @@ def main():
     ap.add_argument('--child', action='store_true', help='(child) measure in this process')
     ap.add_argument('--repeats', type=int, default=12)
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--matching', action='store_true', help='also time fslr_pair_matching on the same batch')
     ap.add_argument('--limit', type=int, default=420, help='seconds for the run')
     ap.add_argument('--out', default=os.path.join(REPO, 'profiles', 'score', 'score_timing.jsonl'))
     args = ap.parse_args()
     if args.child:
-        run(args.repeats, args.warmup)
+        run(args.repeats, args.warmup, args.matching)
         return 0
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     # a fresh child under its own limit; a failure writes nothing
     r = subprocess.run(['timeout', '-k', '10', str(args.limit), sys.executable, os.path.abspath(__file__), '--child',
-                        '--repeats', str(args.repeats), '--warmup', str(args.warmup)], capture_output=True, text=True)
+                        '--repeats', str(args.repeats), '--warmup', str(args.warmup)] +
+                       (['--matching'] if args.matching else []), capture_output=True, text=True)
     sys.stderr.write(r.stderr[-2000:])
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith('{')]
     for ln in lines:
         print(ln, flush=True)
-    if r.returncode != 0 or len(lines) != 2:
+    if r.returncode != 0 or len(lines) != 2 + args.matching:
         print(f'exit status {r.returncode}; nothing written', file=sys.stderr)
         return r.returncode or 1
     with open(args.out, 'w') as fh:
