@@ -51,7 +51,8 @@ EXPORTED = ['fslr_abi_version', 'fslr_last_error', 'fslr_ctx_create', 'fslr_ctx_
             'fslr_match_reads', 'fslr_match_rows', 'fslr_match_timings', 'fslr_score_pairs_any',
             'fslr_match_reads_any', 'fslr_match_rows_any', 'fslr_append_reads', 'fslr_append_timings',
             'fslr_remove_reads', 'fslr_remove_timings', 'fslr_append_reads_any', 'fslr_remove_reads_any',
-            'fslr_pair_matching', 'fslr_pair_matching_any', 'fslr_pair_matching_timings']
+            'fslr_pair_matching', 'fslr_pair_matching_any', 'fslr_pair_matching_timings',
+            'fslr_cluster_loci', 'fslr_get_cluster_loci', 'fslr_cluster_loci_timings']
 # fslr_score_pairs' flag bits (include/fslr_hip.h)
 SCORE_GATE, SCORE_EDGE, SCORE_ZD_GATE, SCORE_ZD_OVERLAP = 1, 2, 4, 8
 # fslr_coverage_*: keys per tile of the sorted arrays, queries per chunk (include/fslr_hip.h)
@@ -269,6 +270,9 @@ def load(path: str = LIB_PATH):
         'fslr_assign_clusters': (ctypes.c_int, [vp, i64, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int64)]),
         'fslr_choose_representatives': (ctypes.c_int, [vp, i64, vp, vp, vp, vp, i64, vp, vp]),
         'fslr_cluster_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        'fslr_cluster_loci': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64)]),
+        'fslr_get_cluster_loci': (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, i64]),
+        'fslr_cluster_loci_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1293,3 +1297,23 @@ class Context:
         ms = (ctypes.c_float * 3)()
         self._check(self._L.fslr_cluster_timings(self._h, ms))
         return dict(zip(('table', 'assign', 'choose'), (float(x) for x in ms)))
+
+    # -- cluster loci (fslr_hip.h fslr_cluster_loci) ---------------------------------------------------
+    def cluster_loci(self):
+        """The merged spans of each cluster's intervals per chromosome, from the resident index and cluster
+        table: ``(off int64[n_clusters + 1], chrom, start, end, n_intervals, n_reads)`` (int32 per row, dense
+        chromosome ids), rows ordered by (cluster, chrom, start)."""
+        n = ctypes.c_int64(0)
+        self._check(self._L.fslr_cluster_loci(self._h, ctypes.byref(n)))
+        nr = int(n.value)
+        ci = getattr(self, '_cluster_info', None) or {'n_clusters': 0}
+        off = np.zeros(ci['n_clusters'] + 1, np.int64)
+        cols = [np.empty(nr, np.int32) for _ in range(5)]
+        self._check(self._L.fslr_get_cluster_loci(self._h, _ptr(off), *(_ptr(x) for x in cols), nr))
+        return (off, *cols)
+
+    def cluster_loci_timings(self) -> dict:
+        """HIP-event time (ms) of the last cluster_loci (profiling contexts)."""
+        ms = (ctypes.c_float * 1)()
+        self._check(self._L.fslr_cluster_loci_timings(self._h, ms))
+        return {'loci': float(ms[0])}

@@ -51,7 +51,7 @@ __all__ = ['IntervalItem', 'keep_fillings', 'rename_chromosomes', 'chrom_to_str'
            'ClusterGraph', 'DeviceIntervalIndex', 'ChromosomeView', 'MultiGpuIndex', 'EdgeCapWarning',
            'calculate_overlap', 'overall_jaccard_similarity', 'different_lengths_or_alignments', 'PairScores',
            'PairMatching',
-           'device_coverage', 'DeviceCoverage', 'ClusterTable', 'cluster_table']
+           'device_coverage', 'DeviceCoverage', 'ClusterTable', 'cluster_table', 'ClusterLoci']
 
 
 class EdgeCapWarning(UserWarning):
@@ -535,6 +535,30 @@ class ReadMatches:
         return off, lab, join
 
 
+class ClusterLoci:
+    """DeviceIntervalIndex.cluster_loci's result (fslr_cluster_loci): per cluster and chromosome the merged
+    spans of the cluster's reads' intervals.  Cluster k's rows are ``off[k]:off[k + 1]`` of ``chrom`` (the
+    chromosome values the index was built with), ``start``, ``end`` (end-inclusive, the largest end in the
+    locus), ``n_intervals`` and ``n_reads`` (distinct reads among them); rows are ordered by (cluster, the
+    index's dense chromosome id, start).  ``chrom_id`` keeps the dense ids."""
+
+    def __init__(self, off, chrom, start, end, n_intervals, n_reads, chrom_id):
+        self.off, self.chrom, self.start, self.end = off, chrom, start, end
+        self.n_intervals, self.n_reads, self.chrom_id = n_intervals, n_reads, chrom_id
+
+    def __len__(self):
+        return int(self.start.shape[0])
+
+    def cluster_of_row(self) -> np.ndarray:
+        """The dense cluster id of every row."""
+        return np.repeat(np.arange(self.off.shape[0] - 1, dtype=np.int64), np.diff(self.off))
+
+    def to_frame(self):
+        """One row per locus: ``cluster``, ``chrom``, ``start``, ``end``, ``n_intervals``, ``n_reads``."""
+        return pd.DataFrame({'cluster': self.cluster_of_row(), 'chrom': self.chrom, 'start': self.start,
+                             'end': self.end, 'n_intervals': self.n_intervals, 'n_reads': self.n_reads})
+
+
 # ------------------------------------------------------------------ device stages
 class DeviceIntervalIndex:
     """What build_interval_trees returns: the CSR in HBM plus the sorted interval index."""
@@ -971,6 +995,24 @@ class DeviceIntervalIndex:
             partner, I, U, flags = ctx.match_rows()
         return ReadMatches(off, partner, I, U, flags, counts, best, names, self.data.qnames[self.csr.read_qcode])
 
+    def cluster_loci(self, G_or_labels=None) -> ClusterLoci:
+        """Where each cluster lies: the merged spans of its reads' intervals per chromosome, made on the device
+        from the resident index and cluster table (fslr_cluster_loci).  ``G_or_labels`` None uses the context's
+        resident table; a graph or a vector of min-rank labels makes the table first (cluster_table) - the way
+        in for an index with reads of more than 64 intervals, whose labels live on the host."""
+        if G_or_labels is not None:
+            cluster_table(G_or_labels, ctx=self.ctx)
+        off, dense, start, end, n_intervals, n_reads = self.ctx.cluster_loci()
+        table = self._chrom_table()[2]
+        raw = np.asarray(list(table.keys()))
+        if dense.size:
+            inv = np.empty(max(table.values()) + 1, raw.dtype)
+            inv[np.asarray(list(table.values()), np.int64)] = raw
+            chrom = inv[dense]
+        else:
+            chrom = raw[:0]
+        return ClusterLoci(off, chrom, start, end, n_intervals, n_reads, dense)
+
     def __getitem__(self, chrom):
         return ChromosomeView(self, chrom)
 
@@ -1107,6 +1149,11 @@ class MultiGpuIndex:
     def match_reads(self, *args, **kwargs):
         raise NotImplementedError('a multi-GPU index lives in the rank processes and cannot match reads from here; '
                                   'build it with n_gpus=1 to match reads')
+
+    def cluster_loci(self, *args, **kwargs):
+        raise NotImplementedError('a multi-GPU index lives in the rank processes and cannot give cluster loci from '
+                                  'here (fslr_cluster_loci needs the whole index on one context); build it with '
+                                  'n_gpus=1')
 
 
 def _open_context(device: int | None = None) -> Context:

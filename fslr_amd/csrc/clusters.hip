@@ -89,6 +89,15 @@ void fslr_cluster_free(fslr_ctx* c) {
   c->clw = nullptr;
 }
 
+bool fslr_cluster_view(const fslr_ctx* c, const int** cid, int64_t* n, int64_t* n_clusters) {
+  const ClusterWork* w = c->clw;
+  if (!w || !w->built) return false;
+  *cid = w->cid;
+  *n = w->n;
+  *n_clusters = w->n_clusters;
+  return true;
+}
+
 namespace {
 
 // ---- wave helpers -----------------------------------------------------------------------------
@@ -591,6 +600,7 @@ int fslr_cluster_table(fslr_ctx* c, const int32_t* labels, int64_t n, fslr_clust
     }
   }
   w->built = false;
+  fslr_loci_drop(c);                        // the loci belong to the table they were made from
   rc = build_table(c, w, lab, n);
   if (rc != FSLR_OK) {
     (void)hipStreamSynchronize(c->stream);

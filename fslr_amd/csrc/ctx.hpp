@@ -185,6 +185,7 @@ struct fslr_ctx {
   struct RemoveWork* rmw = nullptr;     // fslr_remove_reads' maps and tile counts (remove.hip)
   struct MatchWork* mtw = nullptr;       // fslr_match_reads' block and chunk scratch, its last batch's rows (match.hip)
   struct ClusterWork* clw = nullptr;     // fslr_cluster_table's resident table, the assign / representatives scratch (clusters.hip)
+  struct LociWork* lcw = nullptr;        // fslr_cluster_loci's resident rows, its scratch and its last call's time (loci.hip)
   // reads of more than FSLR_MAX_L intervals (long.hip): the virtual-read map and the long-pair stage
   bool lg_set = false;
   // fslr_set_reads_any: virtual interval k is real interval lg_perm[k] (thresholds arrive in the real
@@ -241,6 +242,11 @@ void fslr_pair_matching_free(fslr_ctx* c);
 void fslr_coverage_free(fslr_ctx* c);
 // frees the resident cluster table and its scratch (clusters.hip)
 void fslr_cluster_free(fslr_ctx* c);
+// the resident cluster table for fslr_cluster_loci (clusters.hip): false without a built table
+bool fslr_cluster_view(const fslr_ctx* c, const int** cid, int64_t* n, int64_t* n_clusters);
+// frees the cluster loci's rows and scratch (loci.hip); fslr_loci_drop forgets the rows alone (a new table)
+void fslr_loci_free(fslr_ctx* c);
+void fslr_loci_drop(fslr_ctx* c);
 // frees the read matching's buffers and its saved batch (match.hip)
 void fslr_match_free(fslr_ctx* c);
 // frees the append's batch scratch and its second set of data-order buffers (append.hip)

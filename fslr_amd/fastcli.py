@@ -240,6 +240,12 @@ def _run(args, basename, tsv, ints, strs, t, pool, ctx_f, state):
         fut_r.result()
     finally:
         wpool.shutdown(wait=True)
+    if args.get('cluster_loci'):
+        # fslr_cluster_loci on the resident table; without one (long reads, a refused device block) the
+        # graph's labels are uploaded first
+        from .main import write_cluster_loci
+        write_cluster_loci(f'{basename}.mappings.cluster_loci.bed', trees.cluster_loci(None if dctx is not None else g),
+                           cmap)
     t['write'] = time.perf_counter() - t3
     # the device buffers go now (the caller's process would free them at exit anyway)
     t5 = time.perf_counter()

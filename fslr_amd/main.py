@@ -109,6 +109,9 @@ def assign_clusters(bed_file: pd.DataFrame, G: cluster.ClusterGraph, ctx=None):
 @click.option('--gpus', required=False, default=1, show_default=True, type=click.IntRange(1, 64),
               help='GPUs for the clustering query: one process per GPU, chromosome-split sweep with RCCL '
                    'exchange (ranks share devices over gloo when fewer are visible)')
+@click.option('--cluster-loci', required=False, is_flag=True,
+              help='Also write {name}.mappings.cluster_loci.bed: per cluster and chromosome the merged spans of its '
+                   "reads' intervals with their interval and read counts (one GPU)")
 @click.option('--timings', required=False, is_flag=True, help='Print per-stage wall times to stderr')
 @click.option('--native-io/--pandas-io', default=True, show_default=True,
               help='Read .mappings.bed and write the outputs with the native threaded reader/writer '
@@ -126,6 +129,8 @@ def pipeline(**args):
     for p in primers:
         if p not in known:
             raise ValueError('Input primer name not in primers.csv', p, known)
+    if args.get('cluster_loci') and (args.get('gpus') or 1) > 1:
+        raise click.UsageError('--cluster-loci needs the whole index on one device: run it with --gpus 1')
     if not os.path.exists(args['out']):
         os.mkdir(args['out'])
     if not args['skip_alignment']:
@@ -217,6 +222,18 @@ def _native_open(path):
     return tsv, bed
 
 
+def write_cluster_loci(path, loci, chrom_to_num_map):
+    """``loci`` (cluster.ClusterLoci, chromosomes as rename_chromosomes' numbers) as a tab-separated file:
+    header ``cluster chrom start end n_intervals n_reads``, chromosome names as in the input, rows in the
+    call's order (cluster, chromosome, start)."""
+    name_of = {v: k for k, v in chrom_to_num_map.items()}
+    cols = [loci.cluster_of_row().tolist(), [name_of[c] for c in loci.chrom.tolist()], loci.start.tolist(),
+            loci.end.tolist(), loci.n_intervals.tolist(), loci.n_reads.tolist()]
+    with open(path, 'w') as fh:
+        fh.write('cluster\tchrom\tstart\tend\tn_intervals\tn_reads\n')
+        fh.writelines('\t'.join(map(str, row)) + '\n' for row in zip(*cols))
+
+
 def _cluster_and_write(args, basename, bed_file, tsv, t):
     chromosome_mask = set()
     if args['cluster_mask']:
@@ -270,6 +287,10 @@ def _cluster_and_write(args, basename, bed_file, tsv, t):
                        bed_representative[added], ingest.factorize_qname(bed_representative))
     else:
         bed_representative.to_csv(f'{basename}.mappings.representative.bed', index=False, sep='\t')
+    if args.get('cluster_loci'):
+        # the graph's labels go to the device table first (a long-read index holds them on the host only)
+        write_cluster_loci(f'{basename}.mappings.cluster_loci.bed', interval_tree.cluster_loci(network),
+                           chrom_to_num_map)
     t['write'] = time.perf_counter() - t3
     if args.get('timings'):
         st = network.stats

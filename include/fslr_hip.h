@@ -693,6 +693,35 @@ int  fslr_choose_representatives(fslr_ctx *ctx, int64_t n_codes, const int64_t *
                                  int64_t *winner_code);
 int  fslr_cluster_timings(fslr_ctx *ctx, float *ms);
 
+/* Cluster loci: per cluster of the resident table and per chromosome, the merged spans of its reads'
+ * intervals (the clustering input, every interval of every member read) and their support.
+ *   Within one (cluster, chromosome) group the intervals are walked in ascending start; an interval opens a
+ *   new locus iff it is the group's first or its start is greater than the largest end seen so far in the
+ *   group (end-inclusive, the index's overlap convention: start == that end merges, start == that end + 1
+ *   does not).  A row per locus: chrom (the context's dense id), start (its first interval's), end (the
+ *   largest end in it), n_intervals, n_reads (distinct real reads among them).  Rows are ordered by
+ *   (cluster, chrom, start); off[n_clusters + 1] gives each cluster's row range.  Reads with cid < 0 give
+ *   nothing; no clusters give 0 rows and off == {0}.  The rows depend on the interval sets alone and are the
+ *   same bytes on every run.
+ *   On a context with virtual reads (reads of more than FSLR_MAX_L intervals) the table must be one of
+ *   n_real labels (a host vector); a chunk's intervals count for its real read, once per locus.
+ * fslr_cluster_loci: computes the rows and keeps them resident (*n_rows, may be NULL); syncs.
+ *   FSLR_ERR_STATE, named in the message: no reads set; no index built (or a partial one: a chromosome or
+ *   position filter, n_shards > 1); no cluster table; a table whose n differs from the context's real read
+ *   count (a stale table after fslr_append_reads* / fslr_remove_reads*).  A failed call leaves the previous
+ *   rows and everything else as they were; a successful call replaces the rows; fslr_cluster_table drops
+ *   them; fslr_ctx_destroy frees them.  The query state, the saved search batch, the score scratch and the
+ *   coverage set are left alone.  FSLR_LOCI_TILE (256, 512, 1024 or 2048; read per call) sets the scan's
+ *   tile for tests.
+ * fslr_get_cluster_loci: D2H of the rows (NULL outputs are skipped): off[n_clusters + 1], the others
+ *   [n_rows].  FSLR_ERR_STATE without rows, FSLR_ERR_INVALID when capacity < n_rows (nothing is written).
+ * fslr_cluster_loci_timings (fslr_set_profiling 1 or 2): HIP-event time (ms[0]), first to last operation
+ *   on the stream, of the last fslr_cluster_loci; FSLR_ERR_STATE when it was not profiled. */
+int  fslr_cluster_loci(fslr_ctx *ctx, int64_t *n_rows);
+int  fslr_get_cluster_loci(fslr_ctx *ctx, int64_t *off, int32_t *chrom, int32_t *start, int32_t *end,
+                           int32_t *n_intervals, int32_t *n_reads, int64_t capacity);
+int  fslr_cluster_loci_timings(fslr_ctx *ctx, float *ms);
+
 /* Match reads that are NOT in the uploaded set against the resident index: for a query read Q, given
  * like a row of fslr_reads (its intervals in the order its loop walks them, dense chromosome ids of the
  * uploaded CSR, folded iv_thr, its qlen2 and n_alignments), what the reference's pair loop
