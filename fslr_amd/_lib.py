@@ -52,7 +52,8 @@ EXPORTED = ['fslr_abi_version', 'fslr_last_error', 'fslr_ctx_create', 'fslr_ctx_
             'fslr_match_reads_any', 'fslr_match_rows_any', 'fslr_append_reads', 'fslr_append_timings',
             'fslr_remove_reads', 'fslr_remove_timings', 'fslr_append_reads_any', 'fslr_remove_reads_any',
             'fslr_pair_matching', 'fslr_pair_matching_any', 'fslr_pair_matching_timings',
-            'fslr_cluster_loci', 'fslr_get_cluster_loci', 'fslr_cluster_loci_timings']
+            'fslr_cluster_loci', 'fslr_get_cluster_loci', 'fslr_cluster_loci_timings',
+            'fslr_cluster_junctions', 'fslr_get_cluster_junctions', 'fslr_cluster_junctions_timings']
 # fslr_score_pairs' flag bits (include/fslr_hip.h)
 SCORE_GATE, SCORE_EDGE, SCORE_ZD_GATE, SCORE_ZD_OVERLAP = 1, 2, 4, 8
 # fslr_coverage_*: keys per tile of the sorted arrays, queries per chunk (include/fslr_hip.h)
@@ -273,6 +274,9 @@ def load(path: str = LIB_PATH):
         'fslr_cluster_loci': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64)]),
         'fslr_get_cluster_loci': (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, i64]),
         'fslr_cluster_loci_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        'fslr_cluster_junctions': (ctypes.c_int, [vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int64)]),
+        'fslr_get_cluster_junctions': (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64]),
+        'fslr_cluster_junctions_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1236,6 +1240,7 @@ class Context:
         call (``labels`` None) or a host vector (int32).  Returns ``{n, n_clusters, n_nodes, max_size}``; the
         table replaces the one before."""
         info = ClusterInfo()
+        self._loci_rows = None                   # fslr_cluster_table drops the loci rows
         if labels is None:
             self._check(self._L.fslr_cluster_table(self._h, None, 0, ctypes.byref(info)))
             n = int(self.n_reads)
@@ -1310,6 +1315,19 @@ class Context:
         off = np.zeros(ci['n_clusters'] + 1, np.int64)
         cols = [np.empty(nr, np.int32) for _ in range(5)]
         self._check(self._L.fslr_get_cluster_loci(self._h, _ptr(off), *(_ptr(x) for x in cols), nr))
+        self._loci_rows = nr
+        return (off, *cols)
+
+    def cluster_loci_rows(self):
+        """cluster_loci's result without making the rows again when this context made them since its last
+        cluster_table (they are copied down as they are); else cluster_loci()."""
+        nr = getattr(self, '_loci_rows', None)
+        if nr is None:
+            return self.cluster_loci()
+        ci = getattr(self, '_cluster_info', None) or {'n_clusters': 0}
+        off = np.zeros(ci['n_clusters'] + 1, np.int64)
+        cols = [np.empty(nr, np.int32) for _ in range(5)]
+        self._check(self._L.fslr_get_cluster_loci(self._h, _ptr(off), *(_ptr(x) for x in cols), nr))
         return (off, *cols)
 
     def cluster_loci_timings(self) -> dict:
@@ -1317,3 +1335,37 @@ class Context:
         ms = (ctypes.c_float * 1)()
         self._check(self._L.fslr_cluster_loci_timings(self._h, ms))
         return {'loci': float(ms[0])}
+
+    # -- cluster junctions (fslr_hip.h fslr_cluster_junctions) ------------------------------------------
+    def cluster_junctions(self, qkey, rev=None):
+        """The junctions each cluster's reads support, from the resident loci rows (cluster_loci first):
+        ``qkey`` (int32) and ``rev`` (uint8 or None = all forward) per CSR interval.  Returns ``(off
+        int64[n_clusters + 1], locus_a, side_a, locus_b, side_b, n_obs, n_reads, bp_a_min, bp_a_max, bp_b_min,
+        bp_b_max)``: loci as global row indices of cluster_loci (int32), sides uint8 (0 left, 1 right), rows
+        ordered by (locus_a * 2 + side_a, locus_b * 2 + side_b)."""
+        qkey = np.ascontiguousarray(qkey, dtype=np.int32)
+        if qkey.ndim != 1:
+            raise ValueError('qkey must be one-dimensional')
+        if rev is not None:
+            rev = np.ascontiguousarray(rev, dtype=np.uint8)
+            if rev.shape != qkey.shape:
+                raise ValueError('rev must have qkey\'s shape')
+        n = ctypes.c_int64(0)
+        # (an empty array still passes an address: NULL keys are an error of their own)
+        self._check(self._L.fslr_cluster_junctions(self._h, _ptr(qkey) if qkey.size else _ptr(np.zeros(1, np.int32)),
+                                                   None if rev is None else _ptr(rev) if rev.size else
+                                                   _ptr(np.zeros(1, np.uint8)), int(qkey.size), ctypes.byref(n)))
+        nr = int(n.value)
+        ci = getattr(self, '_cluster_info', None) or {'n_clusters': 0}
+        off = np.zeros(ci['n_clusters'] + 1, np.int64)
+        la, lb, n_obs, n_reads = (np.empty(nr, np.int32) for _ in range(4))
+        sides, bp = np.empty(nr, np.uint8), np.empty((4, nr), np.int32)
+        self._check(self._L.fslr_get_cluster_junctions(self._h, _ptr(off), _ptr(la), _ptr(lb), _ptr(sides), _ptr(n_obs),
+                                                       _ptr(n_reads), _ptr(bp), nr))
+        return (off, la, sides & 1, lb, sides >> 1, n_obs, n_reads, bp[0], bp[1], bp[2], bp[3])
+
+    def cluster_junctions_timings(self) -> dict:
+        """HIP-event time (ms) of the last cluster_junctions, uploads excluded (profiling contexts)."""
+        ms = (ctypes.c_float * 1)()
+        self._check(self._L.fslr_cluster_junctions_timings(self._h, ms))
+        return {'junctions': float(ms[0])}

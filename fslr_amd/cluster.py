@@ -51,7 +51,8 @@ __all__ = ['IntervalItem', 'keep_fillings', 'rename_chromosomes', 'chrom_to_str'
            'ClusterGraph', 'DeviceIntervalIndex', 'ChromosomeView', 'MultiGpuIndex', 'EdgeCapWarning',
            'calculate_overlap', 'overall_jaccard_similarity', 'different_lengths_or_alignments', 'PairScores',
            'PairMatching',
-           'device_coverage', 'DeviceCoverage', 'ClusterTable', 'cluster_table', 'ClusterLoci']
+           'device_coverage', 'DeviceCoverage', 'ClusterTable', 'cluster_table', 'ClusterLoci',
+           'ClusterJunctions']
 
 
 class EdgeCapWarning(UserWarning):
@@ -559,6 +560,53 @@ class ClusterLoci:
                              'end': self.end, 'n_intervals': self.n_intervals, 'n_reads': self.n_reads})
 
 
+class ClusterJunctions:
+    """DeviceIntervalIndex.cluster_junctions' result (fslr_cluster_junctions): the junctions between locus ends
+    that each cluster's reads support.  Cluster k's rows are ``off[k]:off[k + 1]``.  A row joins end ``side_a``
+    of locus ``locus_a`` to end ``side_b`` of locus ``locus_b`` (row indices of ``loci``, the ClusterLoci the
+    call was made on; side 0 is a locus's left end, 1 its right end), with ``n_obs`` observations from
+    ``n_reads`` distinct reads and the smallest and largest breakpoint seen on either side.  Rows are ordered by
+    (locus_a * 2 + side_a, locus_b * 2 + side_b)."""
+
+    COLUMNS = ('locus_a', 'side_a', 'locus_b', 'side_b', 'n_obs', 'n_reads', 'bp_a_min', 'bp_a_max', 'bp_b_min',
+               'bp_b_max')
+
+    def __init__(self, off, cols, loci):
+        self.off, self.loci = off, loci
+        for name, col in zip(self.COLUMNS, cols):
+            setattr(self, name, col)
+
+    def __len__(self):
+        return int(self.locus_a.shape[0])
+
+    def cluster_of_row(self) -> np.ndarray:
+        """The dense cluster id of every row."""
+        return np.repeat(np.arange(self.off.shape[0] - 1, dtype=np.int64), np.diff(self.off))
+
+    def to_frame(self):
+        """One row per junction: ``cluster, chrom_a, side_a, locus_a, bp_a_min, bp_a_max, chrom_b, side_b,
+        locus_b, bp_b_min, bp_b_max, n_obs, n_reads`` (the chromosomes are the values the index was built with)."""
+        ch = self.loci.chrom
+        return pd.DataFrame({'cluster': self.cluster_of_row(),
+                             'chrom_a': ch[self.locus_a], 'side_a': self.side_a, 'locus_a': self.locus_a,
+                             'bp_a_min': self.bp_a_min, 'bp_a_max': self.bp_a_max,
+                             'chrom_b': ch[self.locus_b], 'side_b': self.side_b, 'locus_b': self.locus_b,
+                             'bp_b_min': self.bp_b_min, 'bp_b_max': self.bp_b_max,
+                             'n_obs': self.n_obs, 'n_reads': self.n_reads})
+
+
+def _rev_bits(strand) -> np.ndarray:
+    """uint8 0/1 of a strand column given as booleans, 0/1 or '+' / '-' ('-' and true values are 1)."""
+    s = np.asarray(strand)
+    if s.dtype.kind in 'USO':
+        txt = s.astype(str)
+        bad = ~((txt == '+') | (txt == '-'))
+        if bad.any():
+            raise ValueError(f"strand holds {txt[bad][0]!r}: booleans, 0/1 or '+' / '-' are taken")
+        return (txt == '-').astype(np.uint8)
+    return (s != 0).astype(np.uint8)
+
+
 # ------------------------------------------------------------------ device stages
 class DeviceIntervalIndex:
     """What build_interval_trees returns: the CSR in HBM plus the sorted interval index."""
@@ -1002,7 +1050,10 @@ class DeviceIntervalIndex:
         in for an index with reads of more than 64 intervals, whose labels live on the host."""
         if G_or_labels is not None:
             cluster_table(G_or_labels, ctx=self.ctx)
-        off, dense, start, end, n_intervals, n_reads = self.ctx.cluster_loci()
+        return self._wrap_loci(self.ctx.cluster_loci())
+
+    def _wrap_loci(self, cols) -> ClusterLoci:
+        off, dense, start, end, n_intervals, n_reads = cols
         table = self._chrom_table()[2]
         raw = np.asarray(list(table.keys()))
         if dense.size:
@@ -1012,6 +1063,37 @@ class DeviceIntervalIndex:
         else:
             chrom = raw[:0]
         return ClusterLoci(off, chrom, start, end, n_intervals, n_reads, dense)
+
+    def cluster_junctions(self, qstart, strand=None, G_or_labels=None) -> ClusterJunctions:
+        """Which pieces each cluster's reads join, and where the breakpoints lie (fslr_cluster_junctions).  A read's
+        intervals in query order form a chain of loci; each consecutive pair is one observation of a junction
+        between two locus ends, and a cluster's rows group them.  ``qstart`` and ``strand`` are aligned with the
+        ``data`` list the index was built from (list order: ``bed.loc[tree.data.index, 'qstart']``); they are
+        permuted to the CSR's order through ``csr.data_pos``.  ``strand`` (booleans, 0/1 or '+' / '-'; None: all
+        forward) says that an interval runs against the query order.  ``G_or_labels`` makes the cluster table
+        first, as for cluster_loci; the loci rows are made when the context holds none.  An index with reads of
+        more than 64 intervals raises NotImplementedError.  A RowsIndex supports the call: its data positions
+        come down with fslr_get_csr on first use."""
+        if self.long is not None:
+            raise NotImplementedError(f'cluster_junctions does not take an index with reads of more than {FSLR_MAX_L} '
+                                      f'intervals')
+        n = int(self.csr.n_intervals)
+        q = np.asarray(qstart)
+        if q.shape != (n,):
+            raise ValueError(f'qstart holds {q.shape} values, the data list {n} intervals')
+        if q.dtype.kind not in 'iu' or (q.size and (q.min() < -(1 << 31) or q.max() >= (1 << 31))):
+            raise ValueError('qstart must hold int32 values')
+        rev = None
+        if strand is not None:
+            rev = _rev_bits(strand)
+            if rev.shape != (n,):
+                raise ValueError(f'strand holds {rev.shape} values, the data list {n} intervals')
+        if G_or_labels is not None:
+            cluster_table(G_or_labels, ctx=self.ctx)
+        pos = np.asarray(self.csr.data_pos, np.int64)
+        loci = self._wrap_loci(self.ctx.cluster_loci_rows())
+        off, *cols = self.ctx.cluster_junctions(q[pos].astype(np.int32), None if rev is None else rev[pos])
+        return ClusterJunctions(off, cols, loci)
 
     def __getitem__(self, chrom):
         return ChromosomeView(self, chrom)
@@ -1154,6 +1236,11 @@ class MultiGpuIndex:
         raise NotImplementedError('a multi-GPU index lives in the rank processes and cannot give cluster loci from '
                                   'here (fslr_cluster_loci needs the whole index on one context); build it with '
                                   'n_gpus=1')
+
+    def cluster_junctions(self, *args, **kwargs):
+        raise NotImplementedError('a multi-GPU index lives in the rank processes and cannot give cluster junctions '
+                                  'from here (fslr_cluster_junctions needs the whole index on one context); build it '
+                                  'with n_gpus=1')
 
 
 def _open_context(device: int | None = None) -> Context:

@@ -186,6 +186,7 @@ struct fslr_ctx {
   struct MatchWork* mtw = nullptr;       // fslr_match_reads' block and chunk scratch, its last batch's rows (match.hip)
   struct ClusterWork* clw = nullptr;     // fslr_cluster_table's resident table, the assign / representatives scratch (clusters.hip)
   struct LociWork* lcw = nullptr;        // fslr_cluster_loci's resident rows, its scratch and its last call's time (loci.hip)
+  struct JunctionWork* jnw = nullptr;    // fslr_cluster_junctions' resident rows, its scratch and its last call's time (junctions.hip)
   // reads of more than FSLR_MAX_L intervals (long.hip): the virtual-read map and the long-pair stage
   bool lg_set = false;
   // fslr_set_reads_any: virtual interval k is real interval lg_perm[k] (thresholds arrive in the real
@@ -247,6 +248,14 @@ bool fslr_cluster_view(const fslr_ctx* c, const int** cid, int64_t* n, int64_t* 
 // frees the cluster loci's rows and scratch (loci.hip); fslr_loci_drop forgets the rows alone (a new table)
 void fslr_loci_free(fslr_ctx* c);
 void fslr_loci_drop(fslr_ctx* c);
+// the resident loci rows for fslr_cluster_junctions (loci.hip): false without rows; rows = [5 x rows_cap] chrom,
+// start, end, n_intervals, n_reads
+bool fslr_loci_view(const fslr_ctx* c, const long long** off, const int** rows, int64_t* rows_cap, int64_t* n_rows,
+                    int64_t* n_clusters);
+// frees the cluster junctions' rows and scratch (junctions.hip); fslr_junctions_drop forgets the rows alone (the
+// loci rows they name are dropped or replaced)
+void fslr_junctions_free(fslr_ctx* c);
+void fslr_junctions_drop(fslr_ctx* c);
 // frees the read matching's buffers and its saved batch (match.hip)
 void fslr_match_free(fslr_ctx* c);
 // frees the append's batch scratch and its second set of data-order buffers (append.hip)

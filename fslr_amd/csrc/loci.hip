@@ -85,6 +85,19 @@ void dfree(T*& p) {
 
 void fslr_loci_drop(fslr_ctx* c) {
   if (c->lcw) c->lcw->have = false;
+  fslr_junctions_drop(c);                   // the junctions name loci rows
+}
+
+bool fslr_loci_view(const fslr_ctx* c, const long long** off, const int** rows, int64_t* rows_cap, int64_t* n_rows,
+                    int64_t* n_clusters) {
+  const LociWork* w = c->lcw;
+  if (!w || !w->have) return false;
+  *off = w->off;
+  *rows = w->rows;
+  *rows_cap = w->rows_cap;
+  *n_rows = w->n_rows;
+  *n_clusters = w->n_clusters;
+  return true;
 }
 
 void fslr_loci_free(fslr_ctx* c) {
@@ -594,6 +607,7 @@ int fslr_cluster_loci(fslr_ctx* c, int64_t* n_rows_out) {
     w->timed = true;
   }
   // install
+  fslr_junctions_drop(c);                   // junctions of the rows that go
   std::swap(w->off, nr.off);
   std::swap(w->rows, nr.rows);
   w->rows_cap = n_rows;

@@ -112,6 +112,9 @@ def assign_clusters(bed_file: pd.DataFrame, G: cluster.ClusterGraph, ctx=None):
 @click.option('--cluster-loci', required=False, is_flag=True,
               help='Also write {name}.mappings.cluster_loci.bed: per cluster and chromosome the merged spans of its '
                    "reads' intervals with their interval and read counts (one GPU)")
+@click.option('--cluster-junctions', required=False, is_flag=True,
+              help='Also write {name}.mappings.cluster_junctions.bed: per cluster the junctions between locus ends '
+                   'that its reads support, with their breakpoints and their observation and read counts (one GPU)')
 @click.option('--timings', required=False, is_flag=True, help='Print per-stage wall times to stderr')
 @click.option('--native-io/--pandas-io', default=True, show_default=True,
               help='Read .mappings.bed and write the outputs with the native threaded reader/writer '
@@ -131,6 +134,8 @@ def pipeline(**args):
             raise ValueError('Input primer name not in primers.csv', p, known)
     if args.get('cluster_loci') and (args.get('gpus') or 1) > 1:
         raise click.UsageError('--cluster-loci needs the whole index on one device: run it with --gpus 1')
+    if args.get('cluster_junctions') and (args.get('gpus') or 1) > 1:
+        raise click.UsageError('--cluster-junctions needs the whole index on one device: run it with --gpus 1')
     if not os.path.exists(args['out']):
         os.mkdir(args['out'])
     if not args['skip_alignment']:
@@ -234,6 +239,43 @@ def write_cluster_loci(path, loci, chrom_to_num_map):
         fh.writelines('\t'.join(map(str, row)) + '\n' for row in zip(*cols))
 
 
+JUNCTION_COLUMNS = ('cluster', 'chrom_a', 'side_a', 'locus_a', 'bp_a_min', 'bp_a_max', 'chrom_b', 'side_b', 'locus_b',
+                    'bp_b_min', 'bp_b_max', 'n_obs', 'n_reads')
+
+
+def junction_inputs(path, rows):
+    """``(qstart, rev)`` of the .mappings.bed rows ``rows`` (file row numbers: ``data.index``) from a narrow read
+    of ``path``.  ``qstart`` is already in the frame of the read's primary alignment, so an interval runs against
+    the query order iff its strand differs from the primary row's: rev = (strand == '-') xor (the primary row's
+    strand == '-').  The primary row is the read's first row with a non-empty ``seq`` (it may be one of the two
+    end rows that clustering drops); a read without one counts as forward."""
+    bed = pd.read_csv(path, sep='\t', usecols=['qname', 'qstart', 'strand', 'seq'], dtype={'seq': str, 'strand': str},
+                      na_filter=False)
+    codes, uniq = pd.factorize(bed['qname'], sort=False)
+    neg = (bed['strand'] == '-').to_numpy()
+    prim = np.flatnonzero((bed['seq'] != '').to_numpy())[::-1]        # descending: a read's first row is written last
+    prim_neg = np.zeros(len(uniq), bool)
+    prim_neg[codes[prim]] = neg[prim]
+    rows = np.asarray(rows, np.int64)
+    return bed['qstart'].to_numpy()[rows], (neg ^ prim_neg[codes])[rows].astype(np.uint8)
+
+
+def write_cluster_junctions(path, bed_path, trees, G_or_labels, chrom_to_num_map):
+    """--cluster-junctions: the junctions of ``trees``' clusters (cluster.ClusterJunctions.to_frame) as a
+    tab-separated file with JUNCTION_COLUMNS, chromosome names as in the input.  An index with reads of more than
+    64 intervals prints a notice and writes nothing."""
+    if getattr(trees, 'long', None) is not None:
+        print('--cluster-junctions: the input holds reads of more than 64 intervals; no junctions file is written.')
+        return False
+    qstart, rev = junction_inputs(bed_path, trees.data.index)
+    frame = trees.cluster_junctions(qstart, rev, G_or_labels).to_frame()
+    name_of = {v: k for k, v in chrom_to_num_map.items()}
+    for col in ('chrom_a', 'chrom_b'):
+        frame[col] = [name_of[c] for c in frame[col].tolist()]
+    frame[list(JUNCTION_COLUMNS)].to_csv(path, sep='\t', index=False)
+    return True
+
+
 def _cluster_and_write(args, basename, bed_file, tsv, t):
     chromosome_mask = set()
     if args['cluster_mask']:
@@ -291,6 +333,10 @@ def _cluster_and_write(args, basename, bed_file, tsv, t):
         # the graph's labels go to the device table first (a long-read index holds them on the host only)
         write_cluster_loci(f'{basename}.mappings.cluster_loci.bed', interval_tree.cluster_loci(network),
                            chrom_to_num_map)
+    if args.get('cluster_junctions'):
+        # the table of --cluster-loci, when it ran, is the graph's: its loci rows are used as they are
+        write_cluster_junctions(f'{basename}.mappings.cluster_junctions.bed', f'{basename}.mappings.bed', interval_tree,
+                                None if args.get('cluster_loci') else network, chrom_to_num_map)
     t['write'] = time.perf_counter() - t3
     if args.get('timings'):
         st = network.stats

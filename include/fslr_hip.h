@@ -722,6 +722,48 @@ int  fslr_get_cluster_loci(fslr_ctx *ctx, int64_t *off, int32_t *chrom, int32_t 
                            int32_t *n_intervals, int32_t *n_reads, int64_t capacity);
 int  fslr_cluster_loci_timings(fslr_ctx *ctx, float *ms);
 
+/* Cluster junctions: which locus ends the reads of each cluster join, and where the breakpoints lie.  On top
+ * of reads, a whole built index, the resident cluster table and the resident loci rows (fslr_cluster_loci).
+ *   Inputs, two caller-owned host arrays in CSR interval order, n_intervals each: iv_qkey, the interval's
+ *   position in its read's query order (qstart in practice; any int32, only the order matters), and iv_rev
+ *   (may be NULL = all 0), 1 when the interval runs against the query order.
+ *   Chain: for every real read r with cid[r] >= 0 and at least two resident intervals, its intervals ordered
+ *   by (iv_qkey ascending, CSR position ascending on equal keys); each consecutive pair (x, y) is one
+ *   observation.  Only resident intervals count: an interval dropped by the mask before the upload is not in
+ *   the chain, its neighbours are consecutive.
+ *   Ends: an interval lies in the one locus row of its read's cluster with its chromosome and
+ *   start <= iv.start <= end (a global row index of fslr_get_cluster_loci).  The chain leaves x at its right
+ *   end (side 1, breakpoint x.end) when rev[x] == 0, else at its left end (side 0, x.start); it enters y at
+ *   its left end (side 0, y.start) when rev[y] == 0, else at its right end (side 1, y.end).  An end is
+ *   e = locus_row * 2 + side.
+ *   Canonical form: the unordered pair, stored as (ea, eb) with ea <= eb, the breakpoints swapped with the
+ *   ends; on ea == eb the smaller breakpoint is stored first.  A read and its reverse complement (order
+ *   reversed, every rev flipped) give identical observations.
+ *   Rows: one per distinct (ea, eb), ordered by (ea, eb), which is cluster order: locus_a, side_a, locus_b,
+ *   side_b, n_obs (observations), n_reads (distinct real reads among them), and the extrema of the two
+ *   breakpoints.  off[n_clusters + 1] gives each cluster's row range.  No clusters, or no clustered read with
+ *   two intervals, give 0 rows and off all zero.  The bytes are the same on every run.
+ * fslr_cluster_junctions: computes the rows and keeps them resident (*n_rows, may be NULL); syncs.
+ *   FSLR_ERR_STATE, named in the message: no reads set; no index built (or a partial one); no cluster table;
+ *   a table whose n differs from the context's real read count (stale after fslr_append_reads* /
+ *   fslr_remove_reads*); no resident loci rows of this table (fslr_cluster_loci first).  FSLR_ERR_INVALID:
+ *   iv_qkey NULL; n_intervals different from the context's; a context with virtual reads (reads of more than
+ *   FSLR_MAX_L intervals are out of scope here); more than 2^30 intervals.  A failed call keeps the previous
+ *   rows, a successful one replaces them; whatever drops or replaces the loci rows (fslr_cluster_table, a
+ *   successful fslr_cluster_loci) drops them; fslr_ctx_destroy frees them.  The query state, the saved
+ *   batches and the loci rows are left alone.
+ * fslr_get_cluster_junctions: D2H of the rows (NULL outputs are skipped): off[n_clusters + 1]; locus_a,
+ *   locus_b, n_obs, n_reads [n_rows]; sides [n_rows] = side_a | side_b << 1; bp [4 x n_rows] = the columns
+ *   a_min, a_max, b_min, b_max one after another.  FSLR_ERR_STATE without rows, FSLR_ERR_INVALID when
+ *   capacity < n_rows (nothing is written).
+ * fslr_cluster_junctions_timings (fslr_set_profiling 1 or 2): HIP-event time (ms[0]) of the last
+ *   fslr_cluster_junctions, from the end of the two columns' upload to the last operation on the stream;
+ *   FSLR_ERR_STATE when it was not profiled. */
+int  fslr_cluster_junctions(fslr_ctx *ctx, const int32_t *iv_qkey, const uint8_t *iv_rev, int64_t n_intervals, int64_t *n_rows);
+int  fslr_get_cluster_junctions(fslr_ctx *ctx, int64_t *off, int32_t *locus_a, int32_t *locus_b, uint8_t *sides /* side_a | side_b << 1 */,
+                                int32_t *n_obs, int32_t *n_reads, int32_t *bp /* [4 x n_rows]: a_min, a_max, b_min, b_max */, int64_t capacity);
+int  fslr_cluster_junctions_timings(fslr_ctx *ctx, float *ms);
+
 /* Match reads that are NOT in the uploaded set against the resident index: for a query read Q, given
  * like a row of fslr_reads (its intervals in the order its loop walks them, dense chromosome ids of the
  * uploaded CSR, folded iv_thr, its qlen2 and n_alignments), what the reference's pair loop
