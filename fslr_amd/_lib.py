@@ -53,7 +53,8 @@ EXPORTED = ['fslr_abi_version', 'fslr_last_error', 'fslr_ctx_create', 'fslr_ctx_
             'fslr_remove_reads', 'fslr_remove_timings', 'fslr_append_reads_any', 'fslr_remove_reads_any',
             'fslr_pair_matching', 'fslr_pair_matching_any', 'fslr_pair_matching_timings',
             'fslr_cluster_loci', 'fslr_get_cluster_loci', 'fslr_cluster_loci_timings',
-            'fslr_cluster_junctions', 'fslr_get_cluster_junctions', 'fslr_cluster_junctions_timings']
+            'fslr_cluster_junctions', 'fslr_get_cluster_junctions', 'fslr_cluster_junctions_timings',
+            'fslr_cluster_paths', 'fslr_get_cluster_paths', 'fslr_cluster_paths_timings']
 # fslr_score_pairs' flag bits (include/fslr_hip.h)
 SCORE_GATE, SCORE_EDGE, SCORE_ZD_GATE, SCORE_ZD_OVERLAP = 1, 2, 4, 8
 # fslr_coverage_*: keys per tile of the sorted arrays, queries per chunk (include/fslr_hip.h)
@@ -277,6 +278,9 @@ def load(path: str = LIB_PATH):
         'fslr_cluster_junctions': (ctypes.c_int, [vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int64)]),
         'fslr_get_cluster_junctions': (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i64]),
         'fslr_cluster_junctions_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        'fslr_cluster_paths': (ctypes.c_int, [vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+        'fslr_get_cluster_paths': (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64]),
+        'fslr_cluster_paths_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1369,3 +1373,39 @@ class Context:
         ms = (ctypes.c_float * 1)()
         self._check(self._L.fslr_cluster_junctions_timings(self._h, ms))
         return {'junctions': float(ms[0])}
+
+    # -- cluster paths (fslr_hip.h fslr_cluster_paths) --------------------------------------------------
+    def cluster_paths(self, qkey, rev=None):
+        """The distinct read structures of each cluster, from the resident loci rows (cluster_loci first):
+        ``qkey`` (int32) and ``rev`` (uint8 or None = all forward) per CSR interval.  Returns ``(off
+        int64[n_clusters + 1], tok_off int64[n_rows + 1], n_reads, first_read, locus, rev, path_of_read,
+        flipped)``: a row's tokens are ``locus`` (global row indices of cluster_loci, int32) and ``rev`` (uint8)
+        at ``tok_off[row]:tok_off[row + 1]``; ``path_of_read`` (int32, -1 for a read alone) and ``flipped``
+        (uint8) are per read; rows ascend lexicographically by their tokens ``locus * 2 + rev``."""
+        qkey = np.ascontiguousarray(qkey, dtype=np.int32)
+        if qkey.ndim != 1:
+            raise ValueError('qkey must be one-dimensional')
+        if rev is not None:
+            rev = np.ascontiguousarray(rev, dtype=np.uint8)
+            if rev.shape != qkey.shape:
+                raise ValueError('rev must have qkey\'s shape')
+        nr, nt = ctypes.c_int64(0), ctypes.c_int64(0)
+        # (an empty array still passes an address: NULL keys are an error of their own)
+        self._check(self._L.fslr_cluster_paths(self._h, _ptr(qkey) if qkey.size else _ptr(np.zeros(1, np.int32)),
+                                               None if rev is None else _ptr(rev) if rev.size else
+                                               _ptr(np.zeros(1, np.uint8)), int(qkey.size), ctypes.byref(nr),
+                                               ctypes.byref(nt)))
+        nr, nt, n = int(nr.value), int(nt.value), int(self.n_reads)
+        ci = getattr(self, '_cluster_info', None) or {'n_clusters': 0}
+        off, tok_off = np.zeros(ci['n_clusters'] + 1, np.int64), np.zeros(nr + 1, np.int64)
+        n_reads, first_read, locus, path = (np.empty(k, np.int32) for k in (nr, nr, nt, n))
+        trev, flipped = np.empty(nt, np.uint8), np.empty(n, np.uint8)
+        self._check(self._L.fslr_get_cluster_paths(self._h, _ptr(off), _ptr(tok_off), _ptr(n_reads), _ptr(first_read),
+                                                   _ptr(locus), _ptr(trev), _ptr(path), _ptr(flipped), nr, nt))
+        return (off, tok_off, n_reads, first_read, locus, trev, path, flipped)
+
+    def cluster_paths_timings(self) -> dict:
+        """HIP-event time (ms) of the last cluster_paths, uploads excluded (profiling contexts)."""
+        ms = (ctypes.c_float * 1)()
+        self._check(self._L.fslr_cluster_paths_timings(self._h, ms))
+        return {'paths': float(ms[0])}

@@ -52,7 +52,7 @@ __all__ = ['IntervalItem', 'keep_fillings', 'rename_chromosomes', 'chrom_to_str'
            'calculate_overlap', 'overall_jaccard_similarity', 'different_lengths_or_alignments', 'PairScores',
            'PairMatching',
            'device_coverage', 'DeviceCoverage', 'ClusterTable', 'cluster_table', 'ClusterLoci',
-           'ClusterJunctions']
+           'ClusterJunctions', 'ClusterPaths']
 
 
 class EdgeCapWarning(UserWarning):
@@ -595,6 +595,67 @@ class ClusterJunctions:
                              'n_obs': self.n_obs, 'n_reads': self.n_reads})
 
 
+class ClusterPaths:
+    """DeviceIntervalIndex.cluster_paths' result (fslr_cluster_paths): the distinct read structures of each
+    cluster.  Cluster k's rows are ``off[k]:off[k + 1]``.  A row is one path, the chain of pieces its reads walk:
+    its tokens are ``locus[tok_off[row]:tok_off[row + 1]]`` (row indices of ``loci``, the ClusterLoci the call was
+    made on) with ``rev`` beside them (1: the piece runs against the path's direction), ``n_reads`` reads of the
+    cluster have it and ``first_read`` is the smallest rank among them.  A path is stored in the smaller of its two
+    reading directions; ``flipped[read]`` says that the read walks it backwards, ``path_of_read[read]`` is its
+    global row (-1 for a read alone).  Rows ascend lexicographically by ``locus * 2 + rev``, a prefix before its
+    extensions.  ``read_names`` are the reads' qnames (or codes) by rank."""
+
+    def __init__(self, off, tok_off, n_reads, first_read, locus, rev, path_of_read, flipped, loci, read_names):
+        self.off, self.tok_off, self.n_reads, self.first_read = off, tok_off, n_reads, first_read
+        self.locus, self.rev, self.path_of_read, self.flipped = locus, rev, path_of_read, flipped
+        self.loci, self.read_names = loci, read_names
+
+    def __len__(self):
+        return int(self.n_reads.shape[0])
+
+    def cluster_of_row(self) -> np.ndarray:
+        """The dense cluster id of every row."""
+        return np.repeat(np.arange(self.off.shape[0] - 1, dtype=np.int64), np.diff(self.off))
+
+    def tokens(self, row):
+        """``(locus, rev)`` of one row: its pieces in path order."""
+        s = slice(int(self.tok_off[row]), int(self.tok_off[row + 1]))
+        return self.locus[s], self.rev[s]
+
+    def _path_in_cluster(self) -> np.ndarray:
+        return np.arange(len(self), dtype=np.int64) - np.repeat(self.off[:-1], np.diff(self.off))
+
+    def to_frame(self):
+        """One row per path: ``cluster, path`` (0-based within its cluster), ``n_reads, n_loci`` (the pieces),
+        ``first_read`` (its qname or code) and ``structure``, ``chrom:start-end:+`` (``-`` for a reversed piece)
+        per piece joined by ``,`` (the chromosomes are the values the index was built with)."""
+        lo = self.loci
+        piece = [f'{c}:{s}-{e}:' for c, s, e in zip(lo.chrom.tolist(), lo.start.tolist(), lo.end.tolist())]
+        toks = [piece[k] + '-+'[r == 0] for k, r in zip(self.locus.tolist(), self.rev.tolist())]
+        to = self.tok_off.tolist()
+        return pd.DataFrame({'cluster': self.cluster_of_row(), 'path': self._path_in_cluster(),
+                             'n_reads': self.n_reads, 'n_loci': np.diff(self.tok_off),
+                             'first_read': np.asarray(self.read_names)[self.first_read],
+                             'structure': np.asarray([','.join(toks[a:b]) for a, b in zip(to[:-1], to[1:])], dtype=object)})
+
+    def read_frame(self):
+        """One row per read: ``qname, cluster, path`` (within its cluster; both -1 for a read alone), ``flipped``."""
+        row = self.path_of_read.astype(np.int64)
+        have = row >= 0
+        safe = np.where(have, row, 0)
+        if len(self):
+            cl = np.where(have, self.cluster_of_row()[safe], -1)
+            path = np.where(have, self._path_in_cluster()[safe], -1)
+        else:
+            cl = path = np.full(row.shape, -1, np.int64)
+        return pd.DataFrame({'qname': np.asarray(self.read_names), 'cluster': cl, 'path': path, 'flipped': self.flipped})
+
+    def dominant(self) -> np.ndarray:
+        """Per cluster the global row with the most reads, ties to the first row."""
+        return np.asarray([a + int(np.argmax(self.n_reads[a:b])) for a, b in zip(self.off[:-1].tolist(), self.off[1:].tolist())],
+                          np.int64)
+
+
 def _rev_bits(strand) -> np.ndarray:
     """uint8 0/1 of a strand column given as booleans, 0/1 or '+' / '-' ('-' and true values are 1)."""
     s = np.asarray(strand)
@@ -1064,18 +1125,11 @@ class DeviceIntervalIndex:
             chrom = raw[:0]
         return ClusterLoci(off, chrom, start, end, n_intervals, n_reads, dense)
 
-    def cluster_junctions(self, qstart, strand=None, G_or_labels=None) -> ClusterJunctions:
-        """Which pieces each cluster's reads join, and where the breakpoints lie (fslr_cluster_junctions).  A read's
-        intervals in query order form a chain of loci; each consecutive pair is one observation of a junction
-        between two locus ends, and a cluster's rows group them.  ``qstart`` and ``strand`` are aligned with the
-        ``data`` list the index was built from (list order: ``bed.loc[tree.data.index, 'qstart']``); they are
-        permuted to the CSR's order through ``csr.data_pos``.  ``strand`` (booleans, 0/1 or '+' / '-'; None: all
-        forward) says that an interval runs against the query order.  ``G_or_labels`` makes the cluster table
-        first, as for cluster_loci; the loci rows are made when the context holds none.  An index with reads of
-        more than 64 intervals raises NotImplementedError.  A RowsIndex supports the call: its data positions
-        come down with fslr_get_csr on first use."""
+    def _chain_inputs(self, who, qstart, strand, G_or_labels):
+        """cluster_junctions' and cluster_paths' arguments: the checked ``qstart`` and ``strand`` in CSR order and
+        the loci rows (the table from ``G_or_labels`` first, the rows made when the context holds none)."""
         if self.long is not None:
-            raise NotImplementedError(f'cluster_junctions does not take an index with reads of more than {FSLR_MAX_L} '
+            raise NotImplementedError(f'{who} does not take an index with reads of more than {FSLR_MAX_L} '
                                       f'intervals')
         n = int(self.csr.n_intervals)
         q = np.asarray(qstart)
@@ -1092,8 +1146,33 @@ class DeviceIntervalIndex:
             cluster_table(G_or_labels, ctx=self.ctx)
         pos = np.asarray(self.csr.data_pos, np.int64)
         loci = self._wrap_loci(self.ctx.cluster_loci_rows())
-        off, *cols = self.ctx.cluster_junctions(q[pos].astype(np.int32), None if rev is None else rev[pos])
+        return q[pos].astype(np.int32), None if rev is None else rev[pos], loci
+
+    def cluster_junctions(self, qstart, strand=None, G_or_labels=None) -> ClusterJunctions:
+        """Which pieces each cluster's reads join, and where the breakpoints lie (fslr_cluster_junctions).  A read's
+        intervals in query order form a chain of loci; each consecutive pair is one observation of a junction
+        between two locus ends, and a cluster's rows group them.  ``qstart`` and ``strand`` are aligned with the
+        ``data`` list the index was built from (list order: ``bed.loc[tree.data.index, 'qstart']``); they are
+        permuted to the CSR's order through ``csr.data_pos``.  ``strand`` (booleans, 0/1 or '+' / '-'; None: all
+        forward) says that an interval runs against the query order.  ``G_or_labels`` makes the cluster table
+        first, as for cluster_loci; the loci rows are made when the context holds none.  An index with reads of
+        more than 64 intervals raises NotImplementedError.  A RowsIndex supports the call: its data positions
+        come down with fslr_get_csr on first use."""
+        qkey, rev, loci = self._chain_inputs('cluster_junctions', qstart, strand, G_or_labels)
+        off, *cols = self.ctx.cluster_junctions(qkey, rev)
         return ClusterJunctions(off, cols, loci)
+
+    def cluster_paths(self, qstart, strand=None, G_or_labels=None) -> ClusterPaths:
+        """The distinct read structures of each cluster and how many reads agree on each (fslr_cluster_paths).  A
+        read's intervals in query order are a chain of (locus, strand) tokens; read from the other strand the
+        chain is reversed with every strand flipped, and the smaller of the two is the read's path.  A cluster's
+        rows are its distinct paths.  The arguments are cluster_junctions': ``qstart`` and ``strand`` aligned with
+        the ``data`` list, ``G_or_labels`` makes the cluster table first; an index with reads of more than 64
+        intervals raises NotImplementedError."""
+        qkey, rev, loci = self._chain_inputs('cluster_paths', qstart, strand, G_or_labels)
+        qn = getattr(self.data, 'qnames', None)
+        code = np.asarray(self.csr.read_qcode)
+        return ClusterPaths(*self.ctx.cluster_paths(qkey, rev), loci, code if qn is None else np.asarray(qn[code]))
 
     def __getitem__(self, chrom):
         return ChromosomeView(self, chrom)
@@ -1241,6 +1320,11 @@ class MultiGpuIndex:
         raise NotImplementedError('a multi-GPU index lives in the rank processes and cannot give cluster junctions '
                                   'from here (fslr_cluster_junctions needs the whole index on one context); build it '
                                   'with n_gpus=1')
+
+    def cluster_paths(self, *args, **kwargs):
+        raise NotImplementedError('a multi-GPU index lives in the rank processes and cannot give cluster paths from '
+                                  'here (fslr_cluster_paths needs the whole index on one context); build it with '
+                                  'n_gpus=1')
 
 
 def _open_context(device: int | None = None) -> Context:

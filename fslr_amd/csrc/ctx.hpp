@@ -187,6 +187,7 @@ struct fslr_ctx {
   struct ClusterWork* clw = nullptr;     // fslr_cluster_table's resident table, the assign / representatives scratch (clusters.hip)
   struct LociWork* lcw = nullptr;        // fslr_cluster_loci's resident rows, its scratch and its last call's time (loci.hip)
   struct JunctionWork* jnw = nullptr;    // fslr_cluster_junctions' resident rows, its scratch and its last call's time (junctions.hip)
+  struct PathWork* ptw = nullptr;        // fslr_cluster_paths' resident rows, its scratch and its last call's time (paths.hip)
   // reads of more than FSLR_MAX_L intervals (long.hip): the virtual-read map and the long-pair stage
   bool lg_set = false;
   // fslr_set_reads_any: virtual interval k is real interval lg_perm[k] (thresholds arrive in the real
@@ -256,6 +257,10 @@ bool fslr_loci_view(const fslr_ctx* c, const long long** off, const int** rows, 
 // loci rows they name are dropped or replaced)
 void fslr_junctions_free(fslr_ctx* c);
 void fslr_junctions_drop(fslr_ctx* c);
+// frees the cluster paths' rows and scratch (paths.hip); fslr_paths_drop forgets the rows alone (the loci rows
+// their tokens name are dropped or replaced)
+void fslr_paths_free(fslr_ctx* c);
+void fslr_paths_drop(fslr_ctx* c);
 // frees the read matching's buffers and its saved batch (match.hip)
 void fslr_match_free(fslr_ctx* c);
 // frees the append's batch scratch and its second set of data-order buffers (append.hip)

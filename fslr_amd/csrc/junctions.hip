@@ -27,6 +27,7 @@
 #include <cstring>
 #include <string>
 
+#include "chain.hpp"
 #include "ctx.hpp"
 #include "fslr_hip.h"
 #include "idxsearch.hpp"
@@ -134,25 +135,6 @@ struct EmitArgs {
   int *val, *bpa, *bpb, *rd;
 };
 
-// the locus row of cluster c that holds (chrom, start): the last of the cluster's rows whose (chrom, start) is
-// not above it; the rows are (chrom, start)-ordered and cover every interval of the cluster's reads
-__device__ __forceinline__ int locus_of(const EmitArgs& a, int c, int chrom, int start) {
-  FSLR_BOUND(c, a.n_clusters);
-  long long lo = a.loff[c], hi = a.loff[c + 1] - 1;
-  lo = max(0ll, min(lo, a.n_loci - 1));
-  hi = max(lo, min(hi, a.n_loci - 1));
-  for (int it = 0; it < 32 && lo < hi; ++it) {      // rows < 2^30: at most 30 halvings
-    const long long mid = (lo + hi + 1) >> 1;
-    FSLR_BOUND(mid, a.n_loci);
-    const int mc = a.lchrom[mid];
-    if (mc < chrom || (mc == chrom && a.lstart[mid] <= start))
-      lo = mid;
-    else
-      hi = mid - 1;
-  }
-  return static_cast<int>(lo);
-}
-
 // 64 / W reads side by side: read r (valid: it exists) on the W-lane group of this lane, interval j = the lane's
 // place in the group.  lds: this wavefront's 64 slots.
 template <int W>
@@ -177,15 +159,7 @@ __device__ __forceinline__ void emit_group(const EmitArgs& a, long long r, bool 
     key = a.qkey[k];
     rv = a.rev ? (a.rev[k] != 0) : 0;
   }
-  // the longest read of the wavefront bounds the rank loop
-  int lmax = len;
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) lmax = max(lmax, __shfl_xor(lmax, d));
-  int rank = 0;
-  for (int i = 0; i < lmax; ++i) {                  // lmax <= W
-    const int ok = __shfl(key, gbase + i);
-    rank += (i < len) && (ok < key || (ok == key && i < j));
-  }
+  const int rank = chain_rank(key, len, j, gbase);
   if (have) {
     const int row = locus_of(a, c, rec.x, rec.y);
     // leaving this interval: its right end when it runs with the query, else its left end; entering it: the other

@@ -86,6 +86,7 @@ void dfree(T*& p) {
 void fslr_loci_drop(fslr_ctx* c) {
   if (c->lcw) c->lcw->have = false;
   fslr_junctions_drop(c);                   // the junctions name loci rows
+  fslr_paths_drop(c);                       // and so do the paths' tokens
 }
 
 bool fslr_loci_view(const fslr_ctx* c, const long long** off, const int** rows, int64_t* rows_cap, int64_t* n_rows,
@@ -608,6 +609,7 @@ int fslr_cluster_loci(fslr_ctx* c, int64_t* n_rows_out) {
   }
   // install
   fslr_junctions_drop(c);                   // junctions of the rows that go
+  fslr_paths_drop(c);                       // and paths
   std::swap(w->off, nr.off);
   std::swap(w->rows, nr.rows);
   w->rows_cap = n_rows;

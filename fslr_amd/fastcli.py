@@ -251,6 +251,11 @@ def _run(args, basename, tsv, ints, strs, t, pool, ctx_f, state):
         from .main import write_cluster_junctions
         write_cluster_junctions(f'{basename}.mappings.cluster_junctions.bed', f'{basename}.mappings.bed', trees,
                                 None if dctx is not None or args.get('cluster_loci') else g, cmap)
+    if args.get('cluster_paths'):
+        from .main import write_cluster_paths
+        write_cluster_paths(f'{basename}.mappings.cluster_paths.bed', f'{basename}.mappings.bed', trees,
+                            None if dctx is not None or args.get('cluster_loci') or args.get('cluster_junctions') else g,
+                            cmap)
     t['write'] = time.perf_counter() - t3
     # the device buffers go now (the caller's process would free them at exit anyway)
     t5 = time.perf_counter()

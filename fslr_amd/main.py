@@ -115,6 +115,9 @@ def assign_clusters(bed_file: pd.DataFrame, G: cluster.ClusterGraph, ctx=None):
 @click.option('--cluster-junctions', required=False, is_flag=True,
               help='Also write {name}.mappings.cluster_junctions.bed: per cluster the junctions between locus ends '
                    'that its reads support, with their breakpoints and their observation and read counts (one GPU)')
+@click.option('--cluster-paths', required=False, is_flag=True,
+              help='Also write {name}.mappings.cluster_paths.bed: per cluster its distinct read structures, the chain '
+                   'of pieces each read walks, with the reads that agree on each (one GPU)')
 @click.option('--timings', required=False, is_flag=True, help='Print per-stage wall times to stderr')
 @click.option('--native-io/--pandas-io', default=True, show_default=True,
               help='Read .mappings.bed and write the outputs with the native threaded reader/writer '
@@ -136,6 +139,8 @@ def pipeline(**args):
         raise click.UsageError('--cluster-loci needs the whole index on one device: run it with --gpus 1')
     if args.get('cluster_junctions') and (args.get('gpus') or 1) > 1:
         raise click.UsageError('--cluster-junctions needs the whole index on one device: run it with --gpus 1')
+    if args.get('cluster_paths') and (args.get('gpus') or 1) > 1:
+        raise click.UsageError('--cluster-paths needs the whole index on one device: run it with --gpus 1')
     if not os.path.exists(args['out']):
         os.mkdir(args['out'])
     if not args['skip_alignment']:
@@ -276,6 +281,24 @@ def write_cluster_junctions(path, bed_path, trees, G_or_labels, chrom_to_num_map
     return True
 
 
+PATH_COLUMNS = ('cluster', 'path', 'n_reads', 'n_loci', 'first_read', 'structure')
+
+
+def write_cluster_paths(path, bed_path, trees, G_or_labels, chrom_to_num_map):
+    """--cluster-paths: the distinct read structures of ``trees``' clusters (cluster.ClusterPaths.to_frame) as a
+    tab-separated file with PATH_COLUMNS, chromosome names as in the input.  An index with reads of more than 64
+    intervals prints a notice and writes nothing."""
+    if getattr(trees, 'long', None) is not None:
+        print('--cluster-paths: the input holds reads of more than 64 intervals; no paths file is written.')
+        return False
+    qstart, rev = junction_inputs(bed_path, trees.data.index)
+    paths = trees.cluster_paths(qstart, rev, G_or_labels)
+    name_of = {v: k for k, v in chrom_to_num_map.items()}
+    paths.loci.chrom = np.asarray([name_of[c] for c in paths.loci.chrom.tolist()], dtype=object)
+    paths.to_frame()[list(PATH_COLUMNS)].to_csv(path, sep='\t', index=False)
+    return True
+
+
 def _cluster_and_write(args, basename, bed_file, tsv, t):
     chromosome_mask = set()
     if args['cluster_mask']:
@@ -337,6 +360,10 @@ def _cluster_and_write(args, basename, bed_file, tsv, t):
         # the table of --cluster-loci, when it ran, is the graph's: its loci rows are used as they are
         write_cluster_junctions(f'{basename}.mappings.cluster_junctions.bed', f'{basename}.mappings.bed', interval_tree,
                                 None if args.get('cluster_loci') else network, chrom_to_num_map)
+    if args.get('cluster_paths'):
+        write_cluster_paths(f'{basename}.mappings.cluster_paths.bed', f'{basename}.mappings.bed', interval_tree,
+                            None if args.get('cluster_loci') or args.get('cluster_junctions') else network,
+                            chrom_to_num_map)
     t['write'] = time.perf_counter() - t3
     if args.get('timings'):
         st = network.stats

@@ -764,6 +764,54 @@ int  fslr_get_cluster_junctions(fslr_ctx *ctx, int64_t *off, int32_t *locus_a, i
                                 int32_t *n_obs, int32_t *n_reads, int32_t *bp /* [4 x n_rows]: a_min, a_max, b_min, b_max */, int64_t capacity);
 int  fslr_cluster_junctions_timings(fslr_ctx *ctx, float *ms);
 
+/* Cluster paths: the distinct read structures of each cluster, the ordered chain of (locus, strand) pieces a
+ * read walks, and how many reads of the cluster agree on each chain.  Two different chains can share every
+ * junction, so the junction rows do not give this.  On top of reads, a whole built index, the resident cluster
+ * table and the resident loci rows of that table (fslr_cluster_loci).
+ *   Inputs, those of fslr_cluster_junctions: iv_qkey[n_intervals] and iv_rev[n_intervals] (may be NULL = all 0),
+ *   caller-owned host arrays in CSR interval order.
+ *   Chain: for every real read r with cid[r] >= 0, one-interval reads included, its resident intervals ordered
+ *   by (iv_qkey ascending, CSR position ascending on equal keys).
+ *   Token: an interval gives t = locus_row * 2 + rev.  locus_row is the global loci row of its read's cluster
+ *   that holds it (the rule of the junctions: same chromosome, start <= iv.start <= end), rev its strand bit.
+ *   Canonical form: the forward sequence is F = (t_0 .. t_{L-1}); the same molecule read from the other strand
+ *   is B = (t_{L-1} ^ 1, .., t_0 ^ 1), the order reversed and every low bit flipped.  The read's path is the
+ *   lexicographically smaller of F and B, and flipped[r] = 1 iff B < F strictly: a palindromic chain F == B
+ *   (only possible for an even length) has flipped = 0.
+ *   Reverse complement: a read and its reverse complement have the same path and opposite flipped, unless the
+ *   chain is palindromic.  This holds for a read with distinct query keys; on equal keys the chain order falls
+ *   back to the CSR position, which a reverse complement does not reverse.
+ *   Rows: one per distinct path, in ascending lexicographic order of the token sequence, a proper prefix before
+ *   its extensions.  That is cluster order: the loci rows are cluster-ordered and a path's first token lies in
+ *   its cluster's rows.  A row holds n_reads (the reads with this path), first_read (the smallest read rank
+ *   among them) and its tokens behind tok_off[n_rows + 1] as locus[n_tokens] and rev[n_tokens].
+ *   off[n_clusters + 1] gives each cluster's row range.  Per read: path_of_read[n] is the global row, -1 for a
+ *   read that is not clustered, and flipped[n] is 0 where path_of_read is -1.  The n_reads of a cluster's rows
+ *   sum to the cluster's size.  No clusters give 0 rows and off all zero.  No hash decides equality and the
+ *   bytes are the same on every run.
+ * fslr_cluster_paths: computes the rows and keeps them resident (*n_rows, *n_tokens, may be NULL); syncs.
+ *   FSLR_ERR_STATE, named in the message: no reads set; no index built (or a partial one); no cluster table;
+ *   a table whose n differs from the context's real read count (stale after fslr_append_reads* /
+ *   fslr_remove_reads*); no resident loci rows of this table (fslr_cluster_loci first).  FSLR_ERR_INVALID:
+ *   iv_qkey NULL; n_intervals different from the context's; a context with virtual reads (reads of more than
+ *   FSLR_MAX_L intervals are out of scope here); more than 2^30 intervals.  A failed call keeps the previous
+ *   rows, a successful one replaces them; whatever drops or replaces the loci rows (fslr_cluster_table, a
+ *   successful fslr_cluster_loci) drops them; fslr_ctx_destroy frees them.  The junction rows, the loci rows,
+ *   the query state, the saved batches, the score scratch and the coverage set are left alone, and
+ *   fslr_cluster_junctions leaves the path rows alone.  The exact grouping is an LSD radix sort over chain
+ *   positions, several tokens per 64-bit key; the environment variable FSLR_PATHS_PACK (1..8, read per call)
+ *   caps the tokens per key and changes no result.
+ * fslr_get_cluster_paths: D2H of the rows (NULL outputs are skipped): off[n_clusters + 1]; tok_off[n_rows + 1];
+ *   n_reads, first_read [n_rows]; locus, rev [n_tokens]; path_of_read, flipped [n reads].  FSLR_ERR_STATE
+ *   without rows, FSLR_ERR_INVALID when row_capacity < n_rows or token_capacity < n_tokens (nothing is written).
+ * fslr_cluster_paths_timings (fslr_set_profiling 1 or 2): HIP-event time (ms[0]) of the last
+ *   fslr_cluster_paths, from the end of the two columns' upload to the last operation on the stream;
+ *   FSLR_ERR_STATE when it was not profiled. */
+int  fslr_cluster_paths(fslr_ctx *ctx, const int32_t *iv_qkey, const uint8_t *iv_rev, int64_t n_intervals, int64_t *n_rows, int64_t *n_tokens);
+int  fslr_get_cluster_paths(fslr_ctx *ctx, int64_t *off, int64_t *tok_off, int32_t *n_reads, int32_t *first_read, int32_t *locus, uint8_t *rev,
+                            int32_t *path_of_read, uint8_t *flipped, int64_t row_capacity, int64_t token_capacity);
+int  fslr_cluster_paths_timings(fslr_ctx *ctx, float *ms);
+
 /* Match reads that are NOT in the uploaded set against the resident index: for a query read Q, given
  * like a row of fslr_reads (its intervals in the order its loop walks them, dense chromosome ids of the
  * uploaded CSR, folded iv_thr, its qlen2 and n_alignments), what the reference's pair loop
