@@ -54,7 +54,8 @@ EXPORTED = ['fslr_abi_version', 'fslr_last_error', 'fslr_ctx_create', 'fslr_ctx_
             'fslr_pair_matching', 'fslr_pair_matching_any', 'fslr_pair_matching_timings',
             'fslr_cluster_loci', 'fslr_get_cluster_loci', 'fslr_cluster_loci_timings',
             'fslr_cluster_junctions', 'fslr_get_cluster_junctions', 'fslr_cluster_junctions_timings',
-            'fslr_cluster_paths', 'fslr_get_cluster_paths', 'fslr_cluster_paths_timings']
+            'fslr_cluster_paths', 'fslr_get_cluster_paths', 'fslr_cluster_paths_timings',
+            'fslr_cluster_junctions_any', 'fslr_cluster_paths_any']
 # fslr_score_pairs' flag bits (include/fslr_hip.h)
 SCORE_GATE, SCORE_EDGE, SCORE_ZD_GATE, SCORE_ZD_OVERLAP = 1, 2, 4, 8
 # fslr_coverage_*: keys per tile of the sorted arrays, queries per chunk (include/fslr_hip.h)
@@ -281,6 +282,8 @@ def load(path: str = LIB_PATH):
         'fslr_cluster_paths': (ctypes.c_int, [vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
         'fslr_get_cluster_paths': (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64]),
         'fslr_cluster_paths_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        'fslr_cluster_junctions_any': (ctypes.c_int, [vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int64)]),
+        'fslr_cluster_paths_any': (ctypes.c_int, [vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1347,18 +1350,50 @@ class Context:
         int64[n_clusters + 1], locus_a, side_a, locus_b, side_b, n_obs, n_reads, bp_a_min, bp_a_max, bp_b_min,
         bp_b_max)``: loci as global row indices of cluster_loci (int32), sides uint8 (0 left, 1 right), rows
         ordered by (locus_a * 2 + side_a, locus_b * 2 + side_b)."""
-        qkey = np.ascontiguousarray(qkey, dtype=np.int32)
-        if qkey.ndim != 1:
+        return self._cluster_junctions('fslr_cluster_junctions', qkey, rev)
+
+    def cluster_junctions_any(self, qkey, rev=None):
+        """cluster_junctions for a context that holds reads of more than 64 intervals (fslr_cluster_junctions_any):
+        ``qkey`` and ``rev`` per interval of the real CSR, in its order (the order set_thresholds takes); a read's
+        chain runs over all its intervals.  On a context without such reads it is cluster_junctions, byte for
+        byte."""
+        return self._cluster_junctions('fslr_cluster_junctions_any', qkey, rev)
+
+    @staticmethod
+    def _chain_columns(qkey, rev):
+        """The two columns as the library takes them: int32 keys (values outside int32 are refused, not wrapped)
+        and uint8 strand bits of the same shape."""
+        q = np.asarray(qkey)
+        if q.ndim != 1:
             raise ValueError('qkey must be one-dimensional')
+        if q.dtype.kind not in 'iub':
+            raise ValueError(f'qkey must hold integers, not {q.dtype}')
+        if q.size and (int(q.min()) < -(1 << 31) or int(q.max()) >= (1 << 31)):
+            raise ValueError('qkey must hold int32 values')
+        q = np.ascontiguousarray(q, dtype=np.int32)
         if rev is not None:
             rev = np.ascontiguousarray(rev, dtype=np.uint8)
-            if rev.shape != qkey.shape:
+            if rev.shape != q.shape:
                 raise ValueError('rev must have qkey\'s shape')
+        return q, rev
+
+    def _cluster_junctions(self, name, qkey, rev):
+        call = getattr(self._L, name)
+        if name.endswith('_any'):
+            qkey, rev = self._chain_columns(qkey, rev)
+        else:
+            qkey = np.ascontiguousarray(qkey, dtype=np.int32)
+            if qkey.ndim != 1:
+                raise ValueError('qkey must be one-dimensional')
+            if rev is not None:
+                rev = np.ascontiguousarray(rev, dtype=np.uint8)
+                if rev.shape != qkey.shape:
+                    raise ValueError('rev must have qkey\'s shape')
         n = ctypes.c_int64(0)
         # (an empty array still passes an address: NULL keys are an error of their own)
-        self._check(self._L.fslr_cluster_junctions(self._h, _ptr(qkey) if qkey.size else _ptr(np.zeros(1, np.int32)),
-                                                   None if rev is None else _ptr(rev) if rev.size else
-                                                   _ptr(np.zeros(1, np.uint8)), int(qkey.size), ctypes.byref(n)))
+        self._check(call(self._h, _ptr(qkey) if qkey.size else _ptr(np.zeros(1, np.int32)),
+                         None if rev is None else _ptr(rev) if rev.size else _ptr(np.zeros(1, np.uint8)),
+                         int(qkey.size), ctypes.byref(n)))
         nr = int(n.value)
         ci = getattr(self, '_cluster_info', None) or {'n_clusters': 0}
         off = np.zeros(ci['n_clusters'] + 1, np.int64)
@@ -1382,20 +1417,38 @@ class Context:
         flipped)``: a row's tokens are ``locus`` (global row indices of cluster_loci, int32) and ``rev`` (uint8)
         at ``tok_off[row]:tok_off[row + 1]``; ``path_of_read`` (int32, -1 for a read alone) and ``flipped``
         (uint8) are per read; rows ascend lexicographically by their tokens ``locus * 2 + rev``."""
-        qkey = np.ascontiguousarray(qkey, dtype=np.int32)
-        if qkey.ndim != 1:
-            raise ValueError('qkey must be one-dimensional')
-        if rev is not None:
-            rev = np.ascontiguousarray(rev, dtype=np.uint8)
-            if rev.shape != qkey.shape:
-                raise ValueError('rev must have qkey\'s shape')
+        return self._cluster_paths('fslr_cluster_paths', qkey, rev)
+
+    def cluster_paths_any(self, qkey, rev=None):
+        """cluster_paths for a context that holds reads of more than 64 intervals (fslr_cluster_paths_any): ``qkey``
+        and ``rev`` per interval of the real CSR, in its order; ``path_of_read`` and ``flipped`` are per real read.
+        On a context without such reads it is cluster_paths, byte for byte."""
+        return self._cluster_paths('fslr_cluster_paths_any', qkey, rev)
+
+    def _n_real_reads(self) -> int:
+        """The reads the per-read outputs of a successful cluster_paths* have: the table's n (the library checked
+        it against the context's real read count; ``n_reads`` counts the chunks of long reads too)."""
+        ci = getattr(self, '_cluster_info', None)
+        return int(ci['n']) if ci else int(self.n_reads)
+
+    def _cluster_paths(self, name, qkey, rev):
+        call = getattr(self._L, name)
+        if name.endswith('_any'):
+            qkey, rev = self._chain_columns(qkey, rev)
+        else:
+            qkey = np.ascontiguousarray(qkey, dtype=np.int32)
+            if qkey.ndim != 1:
+                raise ValueError('qkey must be one-dimensional')
+            if rev is not None:
+                rev = np.ascontiguousarray(rev, dtype=np.uint8)
+                if rev.shape != qkey.shape:
+                    raise ValueError('rev must have qkey\'s shape')
         nr, nt = ctypes.c_int64(0), ctypes.c_int64(0)
         # (an empty array still passes an address: NULL keys are an error of their own)
-        self._check(self._L.fslr_cluster_paths(self._h, _ptr(qkey) if qkey.size else _ptr(np.zeros(1, np.int32)),
-                                               None if rev is None else _ptr(rev) if rev.size else
-                                               _ptr(np.zeros(1, np.uint8)), int(qkey.size), ctypes.byref(nr),
-                                               ctypes.byref(nt)))
-        nr, nt, n = int(nr.value), int(nt.value), int(self.n_reads)
+        self._check(call(self._h, _ptr(qkey) if qkey.size else _ptr(np.zeros(1, np.int32)),
+                         None if rev is None else _ptr(rev) if rev.size else _ptr(np.zeros(1, np.uint8)),
+                         int(qkey.size), ctypes.byref(nr), ctypes.byref(nt)))
+        nr, nt, n = int(nr.value), int(nt.value), self._n_real_reads()
         ci = getattr(self, '_cluster_info', None) or {'n_clusters': 0}
         off, tok_off = np.zeros(ci['n_clusters'] + 1, np.int64), np.zeros(nr + 1, np.int64)
         n_reads, first_read, locus, path = (np.empty(k, np.int32) for k in (nr, nr, nt, n))

@@ -1125,10 +1125,10 @@ class DeviceIntervalIndex:
             chrom = raw[:0]
         return ClusterLoci(off, chrom, start, end, n_intervals, n_reads, dense)
 
-    def _chain_inputs(self, who, qstart, strand, G_or_labels):
+    def _chain_inputs(self, who, qstart, strand, G_or_labels, any_length=False):
         """cluster_junctions' and cluster_paths' arguments: the checked ``qstart`` and ``strand`` in CSR order and
         the loci rows (the table from ``G_or_labels`` first, the rows made when the context holds none)."""
-        if self.long is not None:
+        if self.long is not None and not any_length:
             raise NotImplementedError(f'{who} does not take an index with reads of more than {FSLR_MAX_L} '
                                       f'intervals')
         n = int(self.csr.n_intervals)
@@ -1161,6 +1161,26 @@ class DeviceIntervalIndex:
         qkey, rev, loci = self._chain_inputs('cluster_junctions', qstart, strand, G_or_labels)
         off, *cols = self.ctx.cluster_junctions(qkey, rev)
         return ClusterJunctions(off, cols, loci)
+
+    def cluster_junctions_any(self, qstart, strand=None, G_or_labels=None) -> ClusterJunctions:
+        """cluster_junctions for an index that may hold reads of more than 64 intervals, up to 4096
+        (fslr_cluster_junctions_any): a long read's chain runs over all its intervals.  The arguments and the result
+        are cluster_junctions'; ``qstart`` / ``strand`` go through ``csr.data_pos`` to the real CSR's order.  On an
+        index with long reads the labels live on the host, so give ``G_or_labels`` (a graph or a label vector over
+        the real reads) unless cluster_loci made the table already.  On an index without long reads it returns what
+        cluster_junctions returns."""
+        qkey, rev, loci = self._chain_inputs('cluster_junctions_any', qstart, strand, G_or_labels, True)
+        off, *cols = self.ctx.cluster_junctions_any(qkey, rev)
+        return ClusterJunctions(off, cols, loci)
+
+    def cluster_paths_any(self, qstart, strand=None, G_or_labels=None) -> ClusterPaths:
+        """cluster_paths for an index that may hold reads of more than 64 intervals, up to 4096
+        (fslr_cluster_paths_any); the arguments and the result are cluster_paths', the rules for ``G_or_labels``
+        cluster_junctions_any's.  On an index without long reads it returns what cluster_paths returns."""
+        qkey, rev, loci = self._chain_inputs('cluster_paths_any', qstart, strand, G_or_labels, True)
+        qn = getattr(self.data, 'qnames', None)
+        code = np.asarray(self.csr.read_qcode)
+        return ClusterPaths(*self.ctx.cluster_paths_any(qkey, rev), loci, code if qn is None else np.asarray(qn[code]))
 
     def cluster_paths(self, qstart, strand=None, G_or_labels=None) -> ClusterPaths:
         """The distinct read structures of each cluster and how many reads agree on each (fslr_cluster_paths).  A
@@ -1325,6 +1345,12 @@ class MultiGpuIndex:
         raise NotImplementedError('a multi-GPU index lives in the rank processes and cannot give cluster paths from '
                                   'here (fslr_cluster_paths needs the whole index on one context); build it with '
                                   'n_gpus=1')
+
+    def cluster_junctions_any(self, *args, **kwargs):
+        return self.cluster_junctions(*args, **kwargs)
+
+    def cluster_paths_any(self, *args, **kwargs):
+        return self.cluster_paths(*args, **kwargs)
 
 
 def _open_context(device: int | None = None) -> Context:

@@ -51,6 +51,10 @@ struct JunctionWork {
   // per read: cnt, ofs
   int* rbuf = nullptr;               // [2 x (rcap + 1)]
   int64_t rcap = 0;
+  // fslr_cluster_junctions_any on virtual reads: flag, pos and the list of the clustered reads of more than
+  // FSLR_MAX_L intervals
+  int* lbuf = nullptr;               // [3 x (lcap + 1)]
+  int64_t lcap = 0;
   // per observation: sort keys in / out (8 B each; the read flags and their scan reuse the input keys), then
   // seven int columns: vals in (the head flags after the sort), vals out, bp_a, bp_b, read, rid, hpos
   unsigned long long* kbuf = nullptr;   // [2 x (mcap + 1)]
@@ -89,6 +93,7 @@ void fslr_junctions_free(fslr_ctx* c) {
   JunctionWork* w = c->jnw;
   if (!w) return;
   dfree(w->off), dfree(w->rows), dfree(w->sides), dfree(w->qkey), dfree(w->rev), dfree(w->rbuf), dfree(w->kbuf);
+  dfree(w->lbuf);
   dfree(w->mbuf), dfree(w->info), dfree(w->temp);
   if (w->host) (void)hipHostFree(w->host);
   if (w->stage) (void)hipHostFree(w->stage);
@@ -101,13 +106,14 @@ void fslr_junctions_free(fslr_ctx* c) {
 namespace {
 
 // ---- count --------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_jn_count(const int4* __restrict__ rmeta, const int* __restrict__ cid,
-                                                     long long n, int* __restrict__ cnt) {
+// rlen: the real lengths on a context with virtual reads (n = the real reads), else null
+__global__ __launch_bounds__(kBlock) void k_jn_count(const int4* __restrict__ rmeta, const int* __restrict__ rlen,
+                                                     const int* __restrict__ cid, long long n, int* __restrict__ cnt) {
   for (long long r = blockIdx.x * static_cast<long long>(kBlock) + threadIdx.x; r <= n; r += gridDim.x * static_cast<long long>(kBlock)) {
     FSLR_BOUND(r, n + 1);
     int v = 0;
     if (r < n) {
-      const int len = rmeta[r].y & 0xFFFF;
+      const int len = rlen ? rlen[r] : (rmeta[r].y & 0xFFFF);
       if (cid[r] >= 0 && len >= 2) v = len - 1;
     }
     cnt[r] = v;                                     // cnt[n] = 0: the scan's last output is the total
@@ -122,6 +128,9 @@ __global__ void k_jn_last(const int* __restrict__ a, const int* __restrict__ b, 
 // ---- emit ---------------------------------------------------------------------------------------
 struct EmitArgs {
   const int4* rmeta;
+  const int *rlen, *off2;            // the real lists on a context with virtual reads (n = the real reads), else null
+  const int* longs;                  // [n_long] the reads of k_jn_emit_long
+  long long n_long;
   const int4* iv;                    // {chrom, start, end, thr}
   const int* cid;
   const int* qkey;
@@ -145,9 +154,11 @@ __device__ __forceinline__ void emit_group(const EmitArgs& a, long long r, bool 
     FSLR_BOUND(r, a.n);
     const int4 rm = a.rmeta[r];
     first = rm.x;
-    len = rm.y & 0xFFFF;
+    len = a.rlen ? a.rlen[r] : (rm.y & 0xFFFF);
     c = a.cid[r];
-    if (c < 0 || len < 2 || len > W) len = 0;       // len > W never happens: the caller chose W for its reads
+    // len > W: a real read of more than FSLR_MAX_L intervals (k_jn_emit_long's; its first chunk is not a read of
+    // its own); otherwise the caller chose W for its reads
+    if (c < 0 || len < 2 || len > W) len = 0;
   }
   const bool have = j < len;
   int key = 0, rv = 0;
@@ -199,8 +210,8 @@ __global__ __launch_bounds__(kBlock) void k_jn_emit(EmitArgs a) {
     int len = 0;
     if (r16 < a.n) {
       FSLR_BOUND(r16, a.n);
-      len = a.rmeta[r16].y & 0xFFFF;
-      if (a.cid[r16] < 0 || len < 2) len = 0;
+      len = a.rlen ? a.rlen[r16] : (a.rmeta[r16].y & 0xFFFF);
+      if (a.cid[r16] < 0 || len < 2 || len > FSLR_MAX_L) len = 0;
     }
     const bool over16 = __ballot(len > 16) != 0ull, over32 = __ballot(len > 32) != 0ull;
     if (__ballot(len > 0) == 0ull) continue;        // wave-uniform: nothing to write
@@ -214,6 +225,54 @@ __global__ __launch_bounds__(kBlock) void k_jn_emit(EmitArgs a) {
     } else {
       for (int p = 0; p < 4; ++p) emit_group<64>(a, r0 + p, r0 + p < a.n, lane, lds);
     }
+  }
+}
+
+// One workgroup per clustered read of more than FSLR_MAX_L intervals (a.longs): the chain order by an LDS sort,
+// thread t holds rank t: its interval's locus row, then what leaves it into s_w[t] and what enters it into
+// s_in[t]; after the barrier thread t < L - 1 writes observation ofs[r] + t from s_w[t] and s_in[t + 1], as
+// emit_group does.  64 KiB of LDS.
+__global__ __launch_bounds__(kChainBlock) void k_jn_emit_long(EmitArgs a) {
+  __shared__ unsigned long long s_w[kChainMaxL];
+  __shared__ int2 s_in[kChainMaxL];
+  for (long long q = blockIdx.x; q < a.n_long; q += gridDim.x) {
+    FSLR_BOUND(q, a.n_long);
+    const int r = a.longs[q];
+    FSLR_BOUND(r, a.n);
+    const int first = a.rmeta[r].x, len = min(a.rlen[r], kChainMaxL), off2 = a.off2[r], c = a.cid[r];
+    chain_sort_lds(s_w, a.qkey, first, off2, len, a.ni);
+    for (int t = threadIdx.x; t < len; t += kChainBlock) {
+      FSLR_BOUND(t, kChainMaxL);
+      const int j = static_cast<int>(s_w[t] & (kChainMaxL - 1));
+      FSLR_BOUND(j, len);
+      const long long k = list_at(first, off2, j);
+      FSLR_BOUND(k, a.ni);
+      const int4 rec = a.iv[k];
+      const int rv = a.rev ? (a.rev[k] != 0) : 0;
+      const int row = locus_of(a, c, rec.x, rec.y);
+      const unsigned e_out = static_cast<unsigned>(row * 2 + (rv ? 0 : 1)), bp_out = static_cast<unsigned>(rv ? rec.y : rec.z);
+      s_in[t] = make_int2(row * 2 + (rv ? 1 : 0), rv ? rec.z : rec.y);
+      s_w[t] = (static_cast<unsigned long long>(e_out) << 32) | bp_out;     // rank t's own slot: no one else reads its word
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t + 1 < len; t += kChainBlock) {
+      FSLR_BOUND(t + 1, kChainMaxL);
+      const unsigned long long x = s_w[t];
+      const int2 y = s_in[t + 1];
+      int ea = static_cast<int>(x >> 32), ba = static_cast<int>(static_cast<unsigned>(x)), eb = y.x, bb = y.y;
+      if (ea > eb || (ea == eb && ba > bb)) {
+        int u = ea; ea = eb; eb = u;
+        u = ba; ba = bb; bb = u;
+      }
+      const long long o = static_cast<long long>(a.ofs[r]) + t;
+      FSLR_BOUND(o, a.m);
+      a.key[o] = (static_cast<unsigned long long>(static_cast<unsigned>(ea)) << a.kbits) | static_cast<unsigned>(eb);
+      a.val[o] = static_cast<int>(o);
+      a.bpa[o] = ba;
+      a.bpb[o] = bb;
+      a.rd[o] = r;
+    }
+    __syncthreads();                                // the next read writes the arrays again
   }
 }
 
@@ -362,6 +421,21 @@ int up(fslr_ctx* c, JunctionWork* w, void* dst, const void* src, size_t bytes) {
   return FSLR_OK;
 }
 
+// the same for a column the caller gives in the real CSR's order on a context whose intervals were permuted
+// (fslr_set_reads_any): virtual interval k takes src[perm[k]]
+template <typename T>
+int up_perm(fslr_ctx* c, JunctionWork* w, T* dst, const T* src, const std::vector<int>& perm) {
+  const size_t per = kStageBytes / sizeof(T), n = perm.size();
+  T* stage = reinterpret_cast<T*>(w->stage);
+  for (size_t at = 0; at < n; at += per) {
+    const size_t m = std::min(per, n - at);
+    for (size_t k = 0; k < m; ++k) stage[k] = src[perm[at + k]];
+    HIP_TRY(c, hipMemcpyAsync(dst + at, stage, m * sizeof(T), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return FSLR_OK;
+}
+
 int read_last(fslr_ctx* c, JunctionWork* w, const int* a, const int* b, int64_t last, int64_t* out) {
   k_jn_last<<<1, 64, 0, c->stream>>>(a, b, last, w->info);
   HIP_TRY(c, hipGetLastError());
@@ -383,14 +457,12 @@ struct NewRows {
   }
 };
 
-}  // namespace
-
-extern "C" {
-
-int fslr_cluster_junctions(fslr_ctx* c, const int32_t* iv_qkey, const uint8_t* iv_rev, int64_t n_intervals,
-                           int64_t* n_rows_out) {
+// fslr_cluster_junctions (any = false: a context with virtual reads is refused) and fslr_cluster_junctions_any.
+// On a context without virtual reads the two run the same code.
+int junctions_run(fslr_ctx* c, const int32_t* iv_qkey, const uint8_t* iv_rev, int64_t n_intervals, int64_t* n_rows_out,
+                  bool any) {
   if (!c) return FSLR_ERR_INVALID;
-  const char* who = "fslr_cluster_junctions";
+  const char* who = any ? "fslr_cluster_junctions_any" : "fslr_cluster_junctions";
   if (!c->reads_set || c->n == 0) return fail(c, FSLR_ERR_STATE, "fslr_cluster_junctions: no reads set");
   if (int rc = search_state(c, who)) return rc;
   const int* cid = nullptr;
@@ -408,14 +480,19 @@ int fslr_cluster_junctions(fslr_ctx* c, const int32_t* iv_qkey, const uint8_t* i
   int64_t lcap = 0, n_loci = 0, lnc = 0;
   if (!fslr_loci_view(c, &loff, &lrows, &lcap, &n_loci, &lnc) || lnc != nc)
     return fail(c, FSLR_ERR_STATE, "fslr_cluster_junctions: no cluster loci of this table (fslr_cluster_loci first)");
-  if (c->lg_set)
+  if (c->lg_set && !any)
     return fail(c, FSLR_ERR_INVALID, "fslr_cluster_junctions: the context holds reads of more than " +
-                                         std::to_string(FSLR_MAX_L) + " intervals (not supported here)");
+                                         std::to_string(FSLR_MAX_L) + " intervals (fslr_cluster_junctions_any takes them)");
   if (!iv_qkey) return fail(c, FSLR_ERR_INVALID, "fslr_cluster_junctions: iv_qkey is NULL");
   if (n_intervals != c->ni)
     return fail(c, FSLR_ERR_INVALID, "fslr_cluster_junctions: n_intervals " + std::to_string(n_intervals) +
                                          ", the context holds " + std::to_string(c->ni));
-  const int64_t n = c->n, ni = c->ni;
+  // n: the real reads (on a context with virtual reads the chunks behind them are no reads of their own)
+  const bool virt = c->lg_set;
+  const int64_t n = n_real, ni = c->ni;
+  const int *rlen = virt ? c->lg_rlen : nullptr, *off2 = virt ? c->lg_off2 : nullptr;
+  if (virt && !c->lg_perm.empty() && static_cast<int64_t>(c->lg_perm.size()) != ni)
+    return fail(c, FSLR_ERR_STATE, "fslr_cluster_junctions: the interval permutation does not span the intervals (internal)");
   if (ni > kMaxItems || n >= kMaxItems)
     return fail(c, FSLR_ERR_INVALID, "fslr_cluster_junctions: " + std::to_string(ni) +
                                          " intervals: the observations may exceed 2^30");
@@ -442,23 +519,50 @@ int fslr_cluster_junctions(fslr_ctx* c, const int32_t* iv_qkey, const uint8_t* i
     if ((rc = dalloc(c, &w->rbuf, static_cast<size_t>(2 * (n + 1))))) return rc;
     w->rcap = n;
   }
+  if (virt && (n > w->lcap || !w->lbuf)) {
+    w->lcap = 0;
+    if ((rc = dalloc(c, &w->lbuf, static_cast<size_t>(3 * (n + 1))))) return rc;
+    w->lcap = n;
+  }
   int *cnt = w->rbuf, *ofs = w->rbuf + (w->rcap + 1);
+  int *lflag = nullptr, *lpos = nullptr, *longs = nullptr;
+  if (virt) lflag = w->lbuf, lpos = lflag + (w->lcap + 1), longs = lpos + (w->lcap + 1);
   size_t tb = 0;
   HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, cnt, ofs, static_cast<int>(n + 1), st));
   if ((rc = ensure_temp(c, w, tb))) return rc;
   w->timed = false;
   w->ms = 0;
-  if ((rc = up(c, w, w->qkey, iv_qkey, static_cast<size_t>(ni) * sizeof(int)))) return rc;
-  if (iv_rev)
-    if ((rc = up(c, w, w->rev, iv_rev, static_cast<size_t>(ni)))) return rc;
+  if (virt && !c->lg_perm.empty()) {                // the caller's order is the real CSR's
+    if ((rc = up_perm(c, w, w->qkey, iv_qkey, c->lg_perm))) return rc;
+    if (iv_rev)
+      if ((rc = up_perm(c, w, w->rev, iv_rev, c->lg_perm))) return rc;
+  } else {
+    if ((rc = up(c, w, w->qkey, iv_qkey, static_cast<size_t>(ni) * sizeof(int)))) return rc;
+    if (iv_rev)
+      if ((rc = up(c, w, w->rev, iv_rev, static_cast<size_t>(ni)))) return rc;
+  }
   if (c->profiling) HIP_TRY(c, hipEventRecord(w->ev[0], st));     // the two columns are up: the device work from here
-  k_jn_count<<<grid_for(n + 1), kBlock, 0, st>>>(c->rmeta, cid, n, cnt);
+  k_jn_count<<<grid_for(n + 1), kBlock, 0, st>>>(c->rmeta, rlen, cid, n, cnt);
   HIP_TRY(c, hipGetLastError());
   tb = w->temp_bytes;
   HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(w->temp, tb, cnt, ofs, static_cast<int>(n + 1), st));
   int64_t m = 0;
   if ((rc = read_last(c, w, ofs, nullptr, n, &m))) return rc;
   if (m < 0 || m >= ni) return fail(c, FSLR_ERR_STATE, "fslr_cluster_junctions: inconsistent counts (internal)");
+  // the clustered reads of more than FSLR_MAX_L intervals: flag, scan, compact
+  int64_t n_long = 0;
+  if (virt && m > 0) {
+    k_chain_long_flag<<<grid_for(n + 1), kChainBlock, 0, st>>>(cid, rlen, n, lflag);
+    HIP_TRY(c, hipGetLastError());
+    tb = w->temp_bytes;
+    HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(w->temp, tb, lflag, lpos, static_cast<int>(n + 1), st));
+    if ((rc = read_last(c, w, lpos, nullptr, n, &n_long))) return rc;
+    if (n_long < 0 || n_long > n) return fail(c, FSLR_ERR_STATE, "fslr_cluster_junctions: inconsistent counts (internal)");
+    if (n_long > 0) {
+      k_chain_long_compact<<<grid_for(n), kChainBlock, 0, st>>>(lflag, lpos, n, n_long, longs);
+      HIP_TRY(c, hipGetLastError());
+    }
+  }
   if (m > 0 && n_loci <= 0)
     return fail(c, FSLR_ERR_STATE, "fslr_cluster_junctions: clustered reads without loci rows (internal)");
 
@@ -485,10 +589,14 @@ int fslr_cluster_junctions(fslr_ctx* c, const int32_t* iv_qkey, const uint8_t* i
     HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb_scan, rflag, rsum, mi + 1, st));
     if ((rc = ensure_temp(c, w, std::max(tb_sort, tb_scan)))) return rc;
     const long long n_quads = (n + 3) / 4;
-    EmitArgs ea{c->rmeta, c->iv, cid, w->qkey, iv_rev ? w->rev : nullptr, ofs, loff, lrows, lrows + lcap, lrows + 2 * lcap,
+    EmitArgs ea{c->rmeta, rlen, off2, longs, n_long, c->iv, cid, w->qkey, iv_rev ? w->rev : nullptr, ofs, loff, lrows, lrows + lcap, lrows + 2 * lcap,
                 n, ni, m, n_loci, nc, n_quads, kbits, key_in, val_in, bpa, bpb, rd};
     k_jn_emit<<<grid_for(n_quads, kWavesPerBlock, 256 * 32), kBlock, 0, st>>>(ea);
     HIP_TRY(c, hipGetLastError());
+    if (n_long > 0) {                                // only when such reads exist, one workgroup each
+      k_jn_emit_long<<<grid_for(n_long, 1, 256 * 8), kChainBlock, 0, st>>>(ea);
+      HIP_TRY(c, hipGetLastError());
+    }
     tb = w->temp_bytes;
     HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(w->temp, tb, key_in, key_out, val_in, vo, mi, 0, 2 * kbits, st));
     const int g = grid_for(m + 1);
@@ -529,6 +637,20 @@ int fslr_cluster_junctions(fslr_ctx* c, const int32_t* iv_qkey, const uint8_t* i
   w->have = true;
   if (n_rows_out) *n_rows_out = n_rows;
   return FSLR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fslr_cluster_junctions(fslr_ctx* c, const int32_t* iv_qkey, const uint8_t* iv_rev, int64_t n_intervals,
+                           int64_t* n_rows_out) {
+  return junctions_run(c, iv_qkey, iv_rev, n_intervals, n_rows_out, false);
+}
+
+int fslr_cluster_junctions_any(fslr_ctx* c, const int32_t* iv_qkey, const uint8_t* iv_rev, int64_t n_intervals,
+                               int64_t* n_rows_out) {
+  return junctions_run(c, iv_qkey, iv_rev, n_intervals, n_rows_out, true);
 }
 
 int fslr_get_cluster_junctions(fslr_ctx* c, int64_t* off, int32_t* locus_a, int32_t* locus_b, uint8_t* sides,

@@ -63,6 +63,12 @@ struct PathWork {
   // per read: flag, pos, lens; one more word for the longest
   int* rbuf = nullptr;               // [3 x (rcap + 1) + 1]
   int64_t rcap = 0;
+  // fslr_cluster_paths_any on virtual reads: flag, pos and the list of the clustered reads of more than FSLR_MAX_L
+  // intervals; gstart[g] = the clustered reads of at most g position groups, and its pinned copy
+  int* lbuf = nullptr;               // [3 x (lcap + 1)]
+  int64_t lcap = 0;
+  int* gstart = nullptr;             // [kChainMaxL]
+  int* gstart_host = nullptr;        // [kChainMaxL] pinned
   // per clustered read: sort keys in / out, then seven int columns: reads in / out, head, rid, hl, tsum, hpos
   unsigned long long* kbuf = nullptr;   // [2 x (mcap + 1)]
   int* mbuf = nullptr;                  // [7 x (mcap + 1)]
@@ -100,7 +106,8 @@ void fslr_paths_free(fslr_ctx* c) {
   if (!w) return;
   dfree(w->off), dfree(w->tok_off), dfree(w->rows), dfree(w->locus), dfree(w->rev), dfree(w->path_of_read);
   dfree(w->flipped), dfree(w->qkey), dfree(w->qrev), dfree(w->tok), dfree(w->rbuf), dfree(w->kbuf), dfree(w->mbuf);
-  dfree(w->temp);
+  dfree(w->temp), dfree(w->lbuf), dfree(w->gstart);
+  if (w->gstart_host) (void)hipHostFree(w->gstart_host);
   if (w->host) (void)hipHostFree(w->host);
   if (w->stage) (void)hipHostFree(w->stage);
   if (w->ev_ok)
@@ -112,8 +119,9 @@ void fslr_paths_free(fslr_ctx* c) {
 namespace {
 
 // ---- count and compact --------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_path_count(const int4* __restrict__ rmeta, const int* __restrict__ cid,
-                                                       long long n, int* __restrict__ flag, int* __restrict__ lens,
+// rlen: the real lengths on a context with virtual reads (n = the real reads), else null
+__global__ __launch_bounds__(kBlock) void k_path_count(const int4* __restrict__ rmeta, const int* __restrict__ rlen,
+                                                       const int* __restrict__ cid, long long n, int* __restrict__ flag, int* __restrict__ lens,
                                                        int* __restrict__ path_of_read, unsigned char* __restrict__ flipped) {
   for (long long r = blockIdx.x * static_cast<long long>(kBlock) + threadIdx.x; r <= n; r += gridDim.x * static_cast<long long>(kBlock)) {
     FSLR_BOUND(r, n + 1);
@@ -121,7 +129,7 @@ __global__ __launch_bounds__(kBlock) void k_path_count(const int4* __restrict__ 
     if (r < n) {
       if (cid[r] >= 0) {
         f = 1;
-        l = rmeta[r].y & 0xFFFF;
+        l = rlen ? rlen[r] : (rmeta[r].y & 0xFFFF);
       } else {
         path_of_read[r] = -1;                       // a clustered read's words are k_path_scatter's and k_path_tokens'
         flipped[r] = 0;
@@ -146,6 +154,9 @@ __global__ __launch_bounds__(kBlock) void k_path_compact(const int* __restrict__
 // ---- tokens -------------------------------------------------------------------------------------
 struct TokenArgs {
   const int4* rmeta;
+  const int *rlen, *off2;            // the real lists on a context with virtual reads (n = the real reads), else null
+  const int* longs;                  // [n_long] the reads of k_path_tokens_long
+  long long n_long;
   const int4* iv;                    // {chrom, start, end, thr}
   const int* cid;
   const int* qkey;
@@ -167,9 +178,11 @@ __device__ __forceinline__ void token_group(const TokenArgs& a, long long r, boo
     FSLR_BOUND(r, a.n);
     const int4 rm = a.rmeta[r];
     first = rm.x;
-    len = rm.y & 0xFFFF;
+    len = a.rlen ? a.rlen[r] : (rm.y & 0xFFFF);
     c = a.cid[r];
-    if (c < 0 || len > W) len = 0;                  // len > W never happens: the caller chose W for its reads
+    // len > W: a real read of more than FSLR_MAX_L intervals (k_path_tokens_long's; its first chunk is not a read
+    // of its own); otherwise the caller chose W for its reads
+    if (c < 0 || len > W) len = 0;
   }
   const bool have = j < len;
   int key = 0, rv = 0;
@@ -218,8 +231,8 @@ __global__ __launch_bounds__(kBlock) void k_path_tokens(TokenArgs a) {
     int len = 0;
     if (r16 < a.n) {
       FSLR_BOUND(r16, a.n);
-      len = a.rmeta[r16].y & 0xFFFF;
-      if (a.cid[r16] < 0) len = 0;
+      len = a.rlen ? a.rlen[r16] : (a.rmeta[r16].y & 0xFFFF);
+      if (a.cid[r16] < 0 || len > FSLR_MAX_L) len = 0;
     }
     const bool over16 = __ballot(len > 16) != 0ull, over32 = __ballot(len > 32) != 0ull;
     if (__ballot(len > 0) == 0ull) continue;        // wave-uniform: nothing to write
@@ -236,9 +249,87 @@ __global__ __launch_bounds__(kBlock) void k_path_tokens(TokenArgs a) {
   }
 }
 
+// One workgroup per clustered read of more than FSLR_MAX_L intervals (a.longs): the chain order by an LDS sort,
+// the thread that holds rank t stores its token in s_tok[t]; the first position where the forward and the
+// backward sequence differ is the minimum over the waves' first ballots; the tokens there decide flipped, and
+// the canonical token + 1 of position t goes to the t-th interval of the list.  48 KiB of LDS.
+__global__ __launch_bounds__(kChainBlock) void k_path_tokens_long(TokenArgs a) {
+  __shared__ unsigned long long s_w[kChainMaxL];
+  __shared__ int s_tok[kChainMaxL];
+  __shared__ int s_min[kChainBlock / kWave];
+  const int lane = lane_id(), wv = threadIdx.x / kWave;
+  for (long long q = blockIdx.x; q < a.n_long; q += gridDim.x) {
+    FSLR_BOUND(q, a.n_long);
+    const int r = a.longs[q];
+    FSLR_BOUND(r, a.n);
+    const int first = a.rmeta[r].x, len = min(a.rlen[r], kChainMaxL), off2 = a.off2[r], c = a.cid[r];
+    chain_sort_lds(s_w, a.qkey, first, off2, len, a.ni);
+    for (int t = threadIdx.x; t < len; t += kChainBlock) {
+      FSLR_BOUND(t, kChainMaxL);
+      const int j = static_cast<int>(s_w[t] & (kChainMaxL - 1));
+      FSLR_BOUND(j, len);
+      const long long k = list_at(first, off2, j);
+      FSLR_BOUND(k, a.ni);
+      const int4 rec = a.iv[k];
+      s_tok[t] = locus_of(a, c, rec.x, rec.y) * 2 + (a.rev ? (a.rev[k] != 0) : 0);
+    }
+    __syncthreads();
+    // wave wv sees positions base + 64 wv + lane in ascending base: its first ballot with a vote holds its minimum
+    int wmin = kChainMaxL;
+    for (int base = 0; base < len; base += kChainBlock) {          // block-uniform trip count
+      const int t = base + static_cast<int>(threadIdx.x);
+      bool diff = false;
+      if (t < len) {
+        FSLR_BOUND(len - 1 - t, kChainMaxL);
+        diff = s_tok[t] != (s_tok[len - 1 - t] ^ 1);
+      }
+      const unsigned long long vote = __ballot(diff);
+      if (vote != 0ull && wmin == kChainMaxL) wmin = base + wv * kWave + __ffsll(static_cast<long long>(vote)) - 1;
+    }
+    if (lane == 0) s_min[wv] = wmin;
+    __syncthreads();
+    int j0 = s_min[0];
+#pragma unroll
+    for (int k = 1; k < kChainBlock / kWave; ++k) j0 = min(j0, s_min[k]);
+    int flip = 0;
+    if (j0 < len) flip = (s_tok[len - 1 - j0] ^ 1) < s_tok[j0];   // no difference: a palindrome, not flipped
+    for (int t = threadIdx.x; t < len; t += kChainBlock) {
+      const long long k = list_at(first, off2, t);
+      FSLR_BOUND(k, a.ni);
+      a.tok[k] = static_cast<unsigned>(flip ? (s_tok[len - 1 - t] ^ 1) : s_tok[t]) + 1u;
+    }
+    if (threadIdx.x == 0) a.flipped[r] = static_cast<unsigned char>(flip);
+    __syncthreads();                                // the next read writes the arrays again
+  }
+}
+
 // ---- group --------------------------------------------------------------------------------------
+// the position groups of each clustered read, G = ceil(len / p) >= 1: the key of the layout sort
+__global__ __launch_bounds__(kBlock) void k_path_gkeys(const int* __restrict__ val, RealReads rr, long long m, long long n,
+                                                       int p, int* __restrict__ gk) {
+  for (long long s = blockIdx.x * static_cast<long long>(kBlock) + threadIdx.x; s < m; s += gridDim.x * static_cast<long long>(kBlock)) {
+    FSLR_BOUND(s, m);
+    const int r = val[s];
+    FSLR_BOUND(r, n);
+    gk[s] = (rr.len(r, rr.rmeta[r]) + p - 1) / p;
+  }
+}
+
+// gk ascending: gstart[g] = the first s with gk[s] > g, for g in [0, n_groups)
+__global__ __launch_bounds__(kBlock) void k_path_gstart(const int* __restrict__ gk, long long m, int n_groups,
+                                                        int* __restrict__ gstart) {
+  for (long long s = blockIdx.x * static_cast<long long>(kBlock) + threadIdx.x; s <= m; s += gridDim.x * static_cast<long long>(kBlock)) {
+    FSLR_BOUND(s, m + 1);
+    const int g0 = s == 0 ? 0 : gk[s - 1], g1 = s == m ? n_groups : gk[s];
+    for (int g = max(g0, 0); g < min(g1, n_groups); ++g) {
+      FSLR_BOUND(g, n_groups);
+      gstart[g] = static_cast<int>(s);
+    }
+  }
+}
+
 // the sort key of position group [base, base + p): token base in the most significant of the p * kbits bits
-__global__ __launch_bounds__(kBlock) void k_path_keys(const int* __restrict__ val, const int4* __restrict__ rmeta,
+__global__ __launch_bounds__(kBlock) void k_path_keys(const int* __restrict__ val, RealReads rr,
                                                       const unsigned* __restrict__ tok, long long m, long long n,
                                                       long long ni, int base, int p, int kbits,
                                                       unsigned long long* __restrict__ key) {
@@ -246,14 +337,15 @@ __global__ __launch_bounds__(kBlock) void k_path_keys(const int* __restrict__ va
     FSLR_BOUND(s, m);
     const int r = val[s];
     FSLR_BOUND(r, n);
-    const int4 rm = rmeta[r];
-    const int len = rm.y & 0xFFFF;
+    const int4 rm = rr.rmeta[r];
+    const int len = rr.len(r, rm), off2 = rr.second(r, len);
     unsigned long long k = 0;
     for (int i = 0; i < p; ++i) {
       unsigned t = 0;
       if (base + i < len) {
-        FSLR_BOUND(static_cast<long long>(rm.x) + base + i, ni);
-        t = tok[static_cast<long long>(rm.x) + base + i];
+        const long long at = list_at(rm.x, off2, base + i);
+        FSLR_BOUND(at, ni);
+        t = tok[at];
       }
       k = (k << kbits) | t;                         // p * kbits <= 64 and t < 2^kbits: nothing is lost
     }
@@ -261,7 +353,7 @@ __global__ __launch_bounds__(kBlock) void k_path_keys(const int* __restrict__ va
   }
 }
 
-__global__ __launch_bounds__(kBlock) void k_path_heads(const int* __restrict__ val, const int4* __restrict__ rmeta,
+__global__ __launch_bounds__(kBlock) void k_path_heads(const int* __restrict__ val, RealReads rr,
                                                        const unsigned* __restrict__ tok, long long m, long long n,
                                                        long long ni, int* __restrict__ head, int* __restrict__ hl) {
   for (long long s = blockIdx.x * static_cast<long long>(kBlock) + threadIdx.x; s <= m; s += gridDim.x * static_cast<long long>(kBlock)) {
@@ -270,18 +362,19 @@ __global__ __launch_bounds__(kBlock) void k_path_heads(const int* __restrict__ v
     if (s < m) {                                    // the scans run over m + 1: their last outputs are the totals
       const int r = val[s];
       FSLR_BOUND(r, n);
-      const int4 rm = rmeta[r];
-      l = rm.y & 0xFFFF;
+      const int4 rm = rr.rmeta[r];
+      l = rr.len(r, rm);
       h = 1;
       if (s > 0) {
         const int q = val[s - 1];
         FSLR_BOUND(q, n);
-        const int4 qm = rmeta[q];
-        if ((qm.y & 0xFFFF) == l) {
-          FSLR_BOUND(static_cast<long long>(rm.x) + l, ni + 1);
-          FSLR_BOUND(static_cast<long long>(qm.x) + l, ni + 1);
+        const int4 qm = rr.rmeta[q];
+        if (rr.len(q, qm) == l) {
+          const int r2 = rr.second(r, l), q2 = rr.second(q, l);
+          FSLR_BOUND(list_at(rm.x, r2, l - 1), ni);
+          FSLR_BOUND(list_at(qm.x, q2, l - 1), ni);
           int i = 0;
-          while (i < l && tok[static_cast<long long>(rm.x) + i] == tok[static_cast<long long>(qm.x) + i]) ++i;
+          while (i < l && tok[list_at(rm.x, r2, i)] == tok[list_at(qm.x, q2, i)]) ++i;
           h = i < l;
         }
       }
@@ -304,7 +397,7 @@ __global__ __launch_bounds__(kBlock) void k_path_hpos(const int* __restrict__ he
 
 struct RowArgs {
   const int *val, *hpos, *tsum, *head, *rid;
-  const int4* rmeta;
+  RealReads rr;
   const int* cid;
   const unsigned* tok;
   long long m, n, ni, n_rows, n_tokens, n_clusters;
@@ -356,13 +449,13 @@ __global__ __launch_bounds__(kBlock) void k_path_copy(RowArgs a) {
     FSLR_BOUND(p0, a.m);
     const int r = a.val[p0];
     FSLR_BOUND(r, a.n);
-    const int4 rm = a.rmeta[r];
-    const int len = rm.y & 0xFFFF;
+    const int4 rm = a.rr.rmeta[r];
+    const int len = a.rr.len(r, rm), off2 = a.rr.second(r, len);
     const long long o = a.tsum[p0];
     FSLR_BOUND(o + len, a.n_tokens + 1);
-    FSLR_BOUND(static_cast<long long>(rm.x) + len, a.ni + 1);
+    FSLR_BOUND(list_at(rm.x, off2, len - 1), a.ni);
     for (int i = 0; i < len; ++i) {
-      const unsigned t = a.tok[static_cast<long long>(rm.x) + i] - 1u;
+      const unsigned t = a.tok[list_at(rm.x, off2, i)] - 1u;
       a.locus[o + i] = static_cast<int>(t >> 1);
       a.rev[o + i] = static_cast<unsigned char>(t & 1u);
     }
@@ -417,6 +510,21 @@ int up(fslr_ctx* c, PathWork* w, void* dst, const void* src, size_t bytes) {
   return FSLR_OK;
 }
 
+// the same for a column the caller gives in the real CSR's order on a context whose intervals were permuted
+// (fslr_set_reads_any): virtual interval k takes src[perm[k]]
+template <typename T>
+int up_perm(fslr_ctx* c, PathWork* w, T* dst, const T* src, const std::vector<int>& perm) {
+  const size_t per = kStageBytes / sizeof(T), n = perm.size();
+  T* stage = reinterpret_cast<T*>(w->stage);
+  for (size_t at = 0; at < n; at += per) {
+    const size_t m = std::min(per, n - at);
+    for (size_t k = 0; k < m; ++k) stage[k] = src[perm[at + k]];
+    HIP_TRY(c, hipMemcpyAsync(dst + at, stage, m * sizeof(T), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return FSLR_OK;
+}
+
 // two device words to the host; syncs
 int read_two(fslr_ctx* c, PathWork* w, const int* a, const int* b, int64_t* va, int64_t* vb) {
   HIP_TRY(c, hipMemcpyAsync(w->host, a, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -437,14 +545,12 @@ struct NewRows {
   }
 };
 
-}  // namespace
-
-extern "C" {
-
-int fslr_cluster_paths(fslr_ctx* c, const int32_t* iv_qkey, const uint8_t* iv_rev, int64_t n_intervals,
-                       int64_t* n_rows_out, int64_t* n_tokens_out) {
+// fslr_cluster_paths (any = false: a context with virtual reads is refused) and fslr_cluster_paths_any.  On a
+// context without virtual reads the two run the same code.
+int paths_run(fslr_ctx* c, const int32_t* iv_qkey, const uint8_t* iv_rev, int64_t n_intervals, int64_t* n_rows_out,
+              int64_t* n_tokens_out, bool any) {
   if (!c) return FSLR_ERR_INVALID;
-  const char* who = "fslr_cluster_paths";
+  const char* who = any ? "fslr_cluster_paths_any" : "fslr_cluster_paths";
   if (!c->reads_set || c->n == 0) return fail(c, FSLR_ERR_STATE, "fslr_cluster_paths: no reads set");
   if (int rc = search_state(c, who)) return rc;
   const int* cid = nullptr;
@@ -462,14 +568,19 @@ int fslr_cluster_paths(fslr_ctx* c, const int32_t* iv_qkey, const uint8_t* iv_re
   int64_t lcap = 0, n_loci = 0, lnc = 0;
   if (!fslr_loci_view(c, &loff, &lrows, &lcap, &n_loci, &lnc) || lnc != nc)
     return fail(c, FSLR_ERR_STATE, "fslr_cluster_paths: no cluster loci of this table (fslr_cluster_loci first)");
-  if (c->lg_set)
+  if (c->lg_set && !any)
     return fail(c, FSLR_ERR_INVALID, "fslr_cluster_paths: the context holds reads of more than " +
-                                         std::to_string(FSLR_MAX_L) + " intervals (not supported here)");
+                                         std::to_string(FSLR_MAX_L) + " intervals (fslr_cluster_paths_any takes them)");
   if (!iv_qkey) return fail(c, FSLR_ERR_INVALID, "fslr_cluster_paths: iv_qkey is NULL");
   if (n_intervals != c->ni)
     return fail(c, FSLR_ERR_INVALID, "fslr_cluster_paths: n_intervals " + std::to_string(n_intervals) +
                                          ", the context holds " + std::to_string(c->ni));
-  const int64_t n = c->n, ni = c->ni;
+  // n: the real reads (on a context with virtual reads the chunks behind them are no reads of their own)
+  const bool virt = c->lg_set;
+  const int64_t n = n_real, ni = c->ni;
+  const RealReads rr{c->rmeta, virt ? c->lg_rlen : nullptr, virt ? c->lg_off2 : nullptr};
+  if (virt && !c->lg_perm.empty() && static_cast<int64_t>(c->lg_perm.size()) != ni)
+    return fail(c, FSLR_ERR_STATE, "fslr_cluster_paths: the interval permutation does not span the intervals (internal)");
   if (ni > kMaxItems || n >= kMaxItems)
     return fail(c, FSLR_ERR_INVALID, "fslr_cluster_paths: " + std::to_string(ni) + " intervals: more than 2^30");
   HIP_TRY(c, hipSetDevice(c->device));
@@ -495,6 +606,19 @@ int fslr_cluster_paths(fslr_ctx* c, const int32_t* iv_qkey, const uint8_t* iv_re
     if ((rc = dalloc(c, &w->rbuf, static_cast<size_t>(3 * (n + 1) + 1)))) return rc;
     w->rcap = n;
   }
+  int *lflag = nullptr, *lpos = nullptr, *longs = nullptr;
+  if (virt) {
+    if (n > w->lcap || !w->lbuf) {
+      w->lcap = 0;
+      if ((rc = dalloc(c, &w->lbuf, static_cast<size_t>(3 * (n + 1))))) return rc;
+      w->lcap = n;
+    }
+    lflag = w->lbuf, lpos = lflag + (w->lcap + 1), longs = lpos + (w->lcap + 1);
+    if (!w->gstart)
+      if ((rc = dalloc(c, &w->gstart, static_cast<size_t>(kChainMaxL)))) return rc;
+    if (!w->gstart_host)
+      HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&w->gstart_host), kChainMaxL * sizeof(int), hipHostMallocDefault));
+  }
   int *flag = w->rbuf, *pos = flag + (w->rcap + 1), *lens = pos + (w->rcap + 1), *dmax = lens + (w->rcap + 1);
   const int n1 = static_cast<int>(n + 1);
   size_t tb_scan = 0, tb_max = 0;
@@ -507,11 +631,17 @@ int fslr_cluster_paths(fslr_ctx* c, const int32_t* iv_qkey, const uint8_t* iv_re
     return rc;
   w->timed = false;
   w->ms = 0;
-  if ((rc = up(c, w, w->qkey, iv_qkey, static_cast<size_t>(ni) * sizeof(int)))) return rc;
-  if (iv_rev)
-    if ((rc = up(c, w, w->qrev, iv_rev, static_cast<size_t>(ni)))) return rc;
+  if (virt && !c->lg_perm.empty()) {                // the caller's order is the real CSR's
+    if ((rc = up_perm(c, w, w->qkey, iv_qkey, c->lg_perm))) return rc;
+    if (iv_rev)
+      if ((rc = up_perm(c, w, w->qrev, iv_rev, c->lg_perm))) return rc;
+  } else {
+    if ((rc = up(c, w, w->qkey, iv_qkey, static_cast<size_t>(ni) * sizeof(int)))) return rc;
+    if (iv_rev)
+      if ((rc = up(c, w, w->qrev, iv_rev, static_cast<size_t>(ni)))) return rc;
+  }
   if (c->profiling) HIP_TRY(c, hipEventRecord(w->ev[0], st));     // the two columns are up: the device work from here
-  k_path_count<<<grid_for(n + 1), kBlock, 0, st>>>(c->rmeta, cid, n, flag, lens, nr.path_of_read, nr.flipped);
+  k_path_count<<<grid_for(n + 1), kBlock, 0, st>>>(c->rmeta, rr.rlen, cid, n, flag, lens, nr.path_of_read, nr.flipped);
   HIP_TRY(c, hipGetLastError());
   size_t tb = w->temp_bytes;
   HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(w->temp, tb, flag, pos, n1, st));
@@ -519,7 +649,7 @@ int fslr_cluster_paths(fslr_ctx* c, const int32_t* iv_qkey, const uint8_t* iv_re
   HIP_TRY(c, hipcub::DeviceReduce::Max(w->temp, tb, lens, dmax, n1, st));
   int64_t m = 0, lmax = 0;
   if ((rc = read_two(c, w, pos + n, dmax, &m, &lmax))) return rc;
-  if (m < 0 || m > n || lmax < 0 || lmax > FSLR_MAX_L || (m > 0) != (lmax > 0))
+  if (m < 0 || m > n || lmax < 0 || lmax > (virt ? FSLR_MAX_ANY_L : FSLR_MAX_L) || (m > 0) != (lmax > 0))
     return fail(c, FSLR_ERR_STATE, "fslr_cluster_paths: inconsistent counts (internal)");
   if (m > 0 && n_loci <= 0)
     return fail(c, FSLR_ERR_STATE, "fslr_cluster_paths: clustered reads without loci rows (internal)");
@@ -550,20 +680,78 @@ int fslr_cluster_paths(fslr_ctx* c, const int32_t* iv_qkey, const uint8_t* iv_re
     k_path_compact<<<grid_for(n), kBlock, 0, st>>>(flag, pos, n, m, val);
     HIP_TRY(c, hipGetLastError());
     const long long n_quads = (n + 3) / 4;
-    TokenArgs ta{c->rmeta, c->iv, cid, w->qkey, iv_rev ? w->qrev : nullptr, loff, lrows, lrows + lcap,
+    // the clustered reads of more than FSLR_MAX_L intervals: flag, scan, compact
+    int64_t n_long = 0;
+    if (virt && lmax > FSLR_MAX_L) {
+      int64_t unused = 0;
+      k_chain_long_flag<<<grid_for(n + 1), kChainBlock, 0, st>>>(cid, rr.rlen, n, lflag);
+      HIP_TRY(c, hipGetLastError());
+      tb = w->temp_bytes;
+      HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(w->temp, tb, lflag, lpos, n1, st));
+      if ((rc = read_two(c, w, lpos + n, lpos + n, &n_long, &unused))) return rc;
+      if (n_long < 1 || n_long > m) return fail(c, FSLR_ERR_STATE, "fslr_cluster_paths: inconsistent counts (internal)");
+      k_chain_long_compact<<<grid_for(n), kChainBlock, 0, st>>>(lflag, lpos, n, n_long, longs);
+      HIP_TRY(c, hipGetLastError());
+    }
+    TokenArgs ta{c->rmeta, rr.rlen, rr.off2, longs, n_long, c->iv, cid, w->qkey, iv_rev ? w->qrev : nullptr, loff, lrows, lrows + lcap,
                  n, ni, n_loci, nc, n_quads, w->tok, nr.flipped};
     k_path_tokens<<<grid_for(n_quads, kWavesPerBlock, 256 * 32), kBlock, 0, st>>>(ta);
     HIP_TRY(c, hipGetLastError());
+    if (n_long > 0) {                                // only when such reads exist, one workgroup each
+      k_path_tokens_long<<<grid_for(n_long, 1, 256 * 8), kChainBlock, 0, st>>>(ta);
+      HIP_TRY(c, hipGetLastError());
+    }
     // the LSD radix over position groups, last to first
     const int n_groups = static_cast<int>((lmax + pack - 1) / pack);
-    for (int grp = n_groups - 1; grp >= 0; --grp) {
-      k_path_keys<<<g, kBlock, 0, st>>>(val, c->rmeta, w->tok, m, n, ni, grp * pack, pack, kbits, key_in);
+    if (!virt) {
+      for (int grp = n_groups - 1; grp >= 0; --grp) {
+        k_path_keys<<<g, kBlock, 0, st>>>(val, rr, w->tok, m, n, ni, grp * pack, pack, kbits, key_in);
+        HIP_TRY(c, hipGetLastError());
+        tb = w->temp_bytes;
+        HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(w->temp, tb, key_in, key_out, val, val_alt, mi, 0, pack * kbits, st));
+        std::swap(val, val_alt);
+      }
+    } else {
+      // The same order from less work: a read of G = ceil(len / pack) groups has key 0 in every
+      // pass grp >= G, so a full pass leaves it in front, in its initial place among such reads.  The reads are
+      // laid out by (G, rank) and pass grp sorts only those of G > grp, the suffix from gstart[grp]: the reads of
+      // G == grp + 1 stand in rank order right before the suffix the earlier passes sorted, the order a full pass
+      // would have met them in.  Both buffers hold the layout, so the part before the suffix is valid in each.
+      int *gk_in = reinterpret_cast<int*>(key_in), *gk_out = reinterpret_cast<int*>(key_out);
+      size_t tb_g = 0;
+      const int gbits = bits_for(static_cast<int64_t>(n_groups) + 1);
+      HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(nullptr, tb_g, gk_in, gk_out, val, val_alt, mi, 0, gbits, st));
+      if ((rc = ensure_temp(c, w, tb_g))) return rc;
+      k_path_gkeys<<<g, kBlock, 0, st>>>(val, rr, m, n, pack, gk_in);
       HIP_TRY(c, hipGetLastError());
       tb = w->temp_bytes;
-      HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(w->temp, tb, key_in, key_out, val, val_alt, mi, 0, pack * kbits, st));
-      std::swap(val, val_alt);
+      HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(w->temp, tb, gk_in, gk_out, val, val_alt, mi, 0, gbits, st));
+      HIP_TRY(c, hipMemcpyAsync(val, val_alt, static_cast<size_t>(m) * sizeof(int), hipMemcpyDeviceToDevice, st));
+      k_path_gstart<<<g, kBlock, 0, st>>>(gk_out, m, n_groups, w->gstart);
+      HIP_TRY(c, hipGetLastError());
+      HIP_TRY(c, hipMemcpyAsync(w->gstart_host, w->gstart, static_cast<size_t>(n_groups) * sizeof(int), hipMemcpyDeviceToHost, st));
+      HIP_TRY(c, hipStreamSynchronize(st));
+      if (n_groups > kChainMaxL || w->gstart_host[0] != 0)
+        return fail(c, FSLR_ERR_STATE, "fslr_cluster_paths: inconsistent counts (internal)");
+      for (int grp = n_groups - 1; grp >= 0; --grp) {
+        const int64_t s0 = w->gstart_host[grp];
+        if (s0 < 0 || s0 >= m || (grp + 1 < n_groups && s0 > w->gstart_host[grp + 1]))
+          return fail(c, FSLR_ERR_STATE, "fslr_cluster_paths: inconsistent counts (internal)");
+        const int cnt = static_cast<int>(m - s0);
+        size_t need = 0;
+        HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(nullptr, need, key_in + s0, key_out + s0, val + s0, val_alt + s0, cnt, 0, pack * kbits, st));
+        if (need > w->temp_bytes) {
+          HIP_TRY(c, hipStreamSynchronize(st));       // the passes in flight use the buffer that goes
+          if ((rc = ensure_temp(c, w, need))) return rc;
+        }
+        k_path_keys<<<grid_for(cnt), kBlock, 0, st>>>(val + s0, rr, w->tok, cnt, n, ni, grp * pack, pack, kbits, key_in + s0);
+        HIP_TRY(c, hipGetLastError());
+        tb = w->temp_bytes;
+        HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(w->temp, tb, key_in + s0, key_out + s0, val + s0, val_alt + s0, cnt, 0, pack * kbits, st));
+        std::swap(val, val_alt);
+      }
     }
-    k_path_heads<<<g, kBlock, 0, st>>>(val, c->rmeta, w->tok, m, n, ni, head, hl);
+    k_path_heads<<<g, kBlock, 0, st>>>(val, rr, w->tok, m, n, ni, head, hl);
     HIP_TRY(c, hipGetLastError());
     tb = w->temp_bytes;
     HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(w->temp, tb, head, rid, mi + 1, st));
@@ -577,7 +765,7 @@ int fslr_cluster_paths(fslr_ctx* c, const int32_t* iv_qkey, const uint8_t* iv_re
       return rc;
     k_path_hpos<<<g, kBlock, 0, st>>>(head, rid, m, n_rows, hpos);
     HIP_TRY(c, hipGetLastError());
-    RowArgs ra{val, hpos, tsum, head, rid, c->rmeta, cid, w->tok, m, n, ni, n_rows, n_tokens, nc,
+    RowArgs ra{val, hpos, tsum, head, rid, rr, cid, w->tok, m, n, ni, n_rows, n_tokens, nc,
                nr.rows, nr.tok_off, nr.off, nr.locus, nr.rev, nr.path_of_read};
     k_path_rows<<<grid_for(n_rows), kBlock, 0, st>>>(ra);
     HIP_TRY(c, hipGetLastError());
@@ -608,6 +796,20 @@ int fslr_cluster_paths(fslr_ctx* c, const int32_t* iv_qkey, const uint8_t* iv_re
   if (n_rows_out) *n_rows_out = n_rows;
   if (n_tokens_out) *n_tokens_out = n_tokens;
   return FSLR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fslr_cluster_paths(fslr_ctx* c, const int32_t* iv_qkey, const uint8_t* iv_rev, int64_t n_intervals,
+                       int64_t* n_rows_out, int64_t* n_tokens_out) {
+  return paths_run(c, iv_qkey, iv_rev, n_intervals, n_rows_out, n_tokens_out, false);
+}
+
+int fslr_cluster_paths_any(fslr_ctx* c, const int32_t* iv_qkey, const uint8_t* iv_rev, int64_t n_intervals,
+                           int64_t* n_rows_out, int64_t* n_tokens_out) {
+  return paths_run(c, iv_qkey, iv_rev, n_intervals, n_rows_out, n_tokens_out, true);
 }
 
 int fslr_get_cluster_paths(fslr_ctx* c, int64_t* off, int64_t* tok_off, int32_t* n_reads, int32_t* first_read,

@@ -250,12 +250,13 @@ def _run(args, basename, tsv, ints, strs, t, pool, ctx_f, state):
         # a second, narrow read of the input for qstart, strand and seq (nothing of it is read without the flag)
         from .main import write_cluster_junctions
         write_cluster_junctions(f'{basename}.mappings.cluster_junctions.bed', f'{basename}.mappings.bed', trees,
-                                None if dctx is not None or args.get('cluster_loci') else g, cmap)
+                                None if dctx is not None or args.get('cluster_loci') else g, cmap,
+                                bool(args.get('cluster_long_reads')))
     if args.get('cluster_paths'):
         from .main import write_cluster_paths
         write_cluster_paths(f'{basename}.mappings.cluster_paths.bed', f'{basename}.mappings.bed', trees,
                             None if dctx is not None or args.get('cluster_loci') or args.get('cluster_junctions') else g,
-                            cmap)
+                            cmap, bool(args.get('cluster_long_reads')))
     t['write'] = time.perf_counter() - t3
     # the device buffers go now (the caller's process would free them at exit anyway)
     t5 = time.perf_counter()

@@ -118,6 +118,10 @@ def assign_clusters(bed_file: pd.DataFrame, G: cluster.ClusterGraph, ctx=None):
 @click.option('--cluster-paths', required=False, is_flag=True,
               help='Also write {name}.mappings.cluster_paths.bed: per cluster its distinct read structures, the chain '
                    'of pieces each read walks, with the reads that agree on each (one GPU)')
+@click.option('--cluster-long-reads', required=False, is_flag=True,
+              help='With --cluster-junctions / --cluster-paths: also take inputs that hold reads of more than 64 '
+                   'intervals (up to 4096; fslr_cluster_junctions_any / fslr_cluster_paths_any) instead of printing a '
+                   'notice and writing no file')
 @click.option('--timings', required=False, is_flag=True, help='Print per-stage wall times to stderr')
 @click.option('--native-io/--pandas-io', default=True, show_default=True,
               help='Read .mappings.bed and write the outputs with the native threaded reader/writer '
@@ -265,15 +269,17 @@ def junction_inputs(path, rows):
     return bed['qstart'].to_numpy()[rows], (neg ^ prim_neg[codes])[rows].astype(np.uint8)
 
 
-def write_cluster_junctions(path, bed_path, trees, G_or_labels, chrom_to_num_map):
+def write_cluster_junctions(path, bed_path, trees, G_or_labels, chrom_to_num_map, long_reads=False):
     """--cluster-junctions: the junctions of ``trees``' clusters (cluster.ClusterJunctions.to_frame) as a
     tab-separated file with JUNCTION_COLUMNS, chromosome names as in the input.  An index with reads of more than
-    64 intervals prints a notice and writes nothing."""
-    if getattr(trees, 'long', None) is not None:
+    64 intervals prints a notice and writes nothing, unless ``long_reads`` (--cluster-long-reads) sends the call
+    through cluster_junctions_any."""
+    if getattr(trees, 'long', None) is not None and not long_reads:
         print('--cluster-junctions: the input holds reads of more than 64 intervals; no junctions file is written.')
         return False
     qstart, rev = junction_inputs(bed_path, trees.data.index)
-    frame = trees.cluster_junctions(qstart, rev, G_or_labels).to_frame()
+    call = trees.cluster_junctions_any if long_reads else trees.cluster_junctions
+    frame = call(qstart, rev, G_or_labels).to_frame()
     name_of = {v: k for k, v in chrom_to_num_map.items()}
     for col in ('chrom_a', 'chrom_b'):
         frame[col] = [name_of[c] for c in frame[col].tolist()]
@@ -284,15 +290,16 @@ def write_cluster_junctions(path, bed_path, trees, G_or_labels, chrom_to_num_map
 PATH_COLUMNS = ('cluster', 'path', 'n_reads', 'n_loci', 'first_read', 'structure')
 
 
-def write_cluster_paths(path, bed_path, trees, G_or_labels, chrom_to_num_map):
+def write_cluster_paths(path, bed_path, trees, G_or_labels, chrom_to_num_map, long_reads=False):
     """--cluster-paths: the distinct read structures of ``trees``' clusters (cluster.ClusterPaths.to_frame) as a
     tab-separated file with PATH_COLUMNS, chromosome names as in the input.  An index with reads of more than 64
-    intervals prints a notice and writes nothing."""
-    if getattr(trees, 'long', None) is not None:
+    intervals prints a notice and writes nothing, unless ``long_reads`` (--cluster-long-reads) sends the call
+    through cluster_paths_any."""
+    if getattr(trees, 'long', None) is not None and not long_reads:
         print('--cluster-paths: the input holds reads of more than 64 intervals; no paths file is written.')
         return False
     qstart, rev = junction_inputs(bed_path, trees.data.index)
-    paths = trees.cluster_paths(qstart, rev, G_or_labels)
+    paths = (trees.cluster_paths_any if long_reads else trees.cluster_paths)(qstart, rev, G_or_labels)
     name_of = {v: k for k, v in chrom_to_num_map.items()}
     paths.loci.chrom = np.asarray([name_of[c] for c in paths.loci.chrom.tolist()], dtype=object)
     paths.to_frame()[list(PATH_COLUMNS)].to_csv(path, sep='\t', index=False)
@@ -359,11 +366,12 @@ def _cluster_and_write(args, basename, bed_file, tsv, t):
     if args.get('cluster_junctions'):
         # the table of --cluster-loci, when it ran, is the graph's: its loci rows are used as they are
         write_cluster_junctions(f'{basename}.mappings.cluster_junctions.bed', f'{basename}.mappings.bed', interval_tree,
-                                None if args.get('cluster_loci') else network, chrom_to_num_map)
+                                None if args.get('cluster_loci') else network, chrom_to_num_map,
+                                bool(args.get('cluster_long_reads')))
     if args.get('cluster_paths'):
         write_cluster_paths(f'{basename}.mappings.cluster_paths.bed', f'{basename}.mappings.bed', interval_tree,
                             None if args.get('cluster_loci') or args.get('cluster_junctions') else network,
-                            chrom_to_num_map)
+                            chrom_to_num_map, bool(args.get('cluster_long_reads')))
     t['write'] = time.perf_counter() - t3
     if args.get('timings'):
         st = network.stats

@@ -812,6 +812,30 @@ int  fslr_get_cluster_paths(fslr_ctx *ctx, int64_t *off, int64_t *tok_off, int32
                             int32_t *path_of_read, uint8_t *flipped, int64_t row_capacity, int64_t token_capacity);
 int  fslr_cluster_paths_timings(fslr_ctx *ctx, float *ms);
 
+/* Cluster junctions and paths for reads of any length: fslr_cluster_junctions / fslr_cluster_paths for a context
+ * that holds virtual reads (fslr_set_reads_any, fslr_set_long_reads), as fslr_score_pairs_any stands beside
+ * fslr_score_pairs.  The contract is the one above, read for real reads of 1..FSLR_MAX_ANY_L intervals.
+ *   Inputs      iv_qkey / iv_rev (may be NULL = all 0) in the REAL CSR's interval order, n_intervals the real
+ *               interval count: the order fslr_set_thresholds takes iv_thr in after fslr_set_reads_any (the call
+ *               brings them to the virtual order itself; after fslr_set_long_reads, where the caller uploaded the
+ *               virtual CSR, the two orders are the same).
+ *   Chain       all the intervals of real read r, the chunks behind its first FSLR_MAX_L included, ordered by
+ *               (iv_qkey ascending, position in the real list ascending on equal keys).  A chunk is never a read
+ *               of its own.
+ *   Table       one of n_real labels (the rule of fslr_cluster_loci); cid, path_of_read and flipped are per real
+ *               read, n_real of them.
+ *   Rows        the resident rows of the plain calls: fslr_get_cluster_junctions, fslr_get_cluster_paths and the
+ *               two _timings calls answer for them, whatever drops or frees those rows drops or frees these, a
+ *               failed call keeps the previous rows.
+ *   Errors      those of the plain calls without the refusal of virtual reads.  FSLR_ERR_INVALID beyond 2^30
+ *               intervals (the observations and the clustered tokens are fewer).
+ *   On a context without virtual reads each call runs the code of its plain call and leaves the same bytes.
+ *   Reads of more than FSLR_MAX_L intervals take one workgroup each (their chain is sorted in LDS); the path
+ *   grouping sorts, in the pass of a position group, only the reads long enough to reach it, so its work is the
+ *   sum of the reads' group counts.  FSLR_PATHS_PACK keeps its meaning.  One GPU: the whole index on the context. */
+int  fslr_cluster_junctions_any(fslr_ctx *ctx, const int32_t *iv_qkey, const uint8_t *iv_rev, int64_t n_intervals, int64_t *n_rows);
+int  fslr_cluster_paths_any(fslr_ctx *ctx, const int32_t *iv_qkey, const uint8_t *iv_rev, int64_t n_intervals, int64_t *n_rows, int64_t *n_tokens);
+
 /* Match reads that are NOT in the uploaded set against the resident index: for a query read Q, given
  * like a row of fslr_reads (its intervals in the order its loop walks them, dense chromosome ids of the
  * uploaded CSR, folded iv_thr, its qlen2 and n_alignments), what the reference's pair loop
