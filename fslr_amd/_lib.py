@@ -55,7 +55,8 @@ EXPORTED = ['fslr_abi_version', 'fslr_last_error', 'fslr_ctx_create', 'fslr_ctx_
             'fslr_cluster_loci', 'fslr_get_cluster_loci', 'fslr_cluster_loci_timings',
             'fslr_cluster_junctions', 'fslr_get_cluster_junctions', 'fslr_cluster_junctions_timings',
             'fslr_cluster_paths', 'fslr_get_cluster_paths', 'fslr_cluster_paths_timings',
-            'fslr_cluster_junctions_any', 'fslr_cluster_paths_any']
+            'fslr_cluster_junctions_any', 'fslr_cluster_paths_any',
+            'fslr_cluster_path_segments', 'fslr_get_cluster_path_segments', 'fslr_cluster_path_segments_timings']
 # fslr_score_pairs' flag bits (include/fslr_hip.h)
 SCORE_GATE, SCORE_EDGE, SCORE_ZD_GATE, SCORE_ZD_OVERLAP = 1, 2, 4, 8
 # fslr_coverage_*: keys per tile of the sorted arrays, queries per chunk (include/fslr_hip.h)
@@ -284,6 +285,9 @@ def load(path: str = LIB_PATH):
         'fslr_cluster_paths_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
         'fslr_cluster_junctions_any': (ctypes.c_int, [vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int64)]),
         'fslr_cluster_paths_any': (ctypes.c_int, [vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+        'fslr_cluster_path_segments': (ctypes.c_int, [vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int64)]),
+        'fslr_get_cluster_path_segments': (ctypes.c_int, [vp, vp, vp, vp, i64]),
+        'fslr_cluster_path_segments_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1462,3 +1466,33 @@ class Context:
         ms = (ctypes.c_float * 1)()
         self._check(self._L.fslr_cluster_paths_timings(self._h, ms))
         return {'paths': float(ms[0])}
+
+    # -- path segments (fslr_hip.h fslr_cluster_path_segments) ------------------------------------------
+    def cluster_path_segments(self, qkey, qend=None):
+        """Consensus coordinates and junction gaps per slot of the resident path rows (cluster_paths first, with the
+        same ``qkey``): ``qkey`` and ``qend`` (int32, or None = no gaps, the gap columns all 0) per CSR interval.
+        Returns nine int32 columns of n_tokens each, in the slots' order (``tok_off`` of cluster_paths):
+        ``(start_min, start_med, start_max, end_min, end_med, end_max, gap_min, gap_med, gap_max)``; the medians are
+        lower medians, a gap is stored at the earlier of the two slots it joins and a row's last slot holds 0."""
+        qkey = np.ascontiguousarray(qkey, dtype=np.int32)
+        if qkey.ndim != 1:
+            raise ValueError('qkey must be one-dimensional')
+        if qend is not None:
+            qend = np.ascontiguousarray(qend, dtype=np.int32)
+            if qend.shape != qkey.shape:
+                raise ValueError('qend must have qkey\'s shape')
+        nt = ctypes.c_int64(0)
+        # (an empty array still passes an address: NULL keys are an error of their own)
+        self._check(self._L.fslr_cluster_path_segments(
+            self._h, _ptr(qkey) if qkey.size else _ptr(np.zeros(1, np.int32)),
+            None if qend is None else _ptr(qend) if qend.size else _ptr(np.zeros(1, np.int32)), int(qkey.size), ctypes.byref(nt)))
+        nt = int(nt.value)
+        start, end, gap = (np.empty((3, nt), np.int32) for _ in range(3))
+        self._check(self._L.fslr_get_cluster_path_segments(self._h, _ptr(start), _ptr(end), _ptr(gap), nt))
+        return (start[0], start[1], start[2], end[0], end[1], end[2], gap[0], gap[1], gap[2])
+
+    def cluster_path_segments_timings(self) -> dict:
+        """HIP-event time (ms) of the last cluster_path_segments, uploads excluded (profiling contexts)."""
+        ms = (ctypes.c_float * 1)()
+        self._check(self._L.fslr_cluster_path_segments_timings(self._h, ms))
+        return {'segments': float(ms[0])}

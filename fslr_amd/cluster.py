@@ -41,7 +41,7 @@ from ._lazy import pandas as pd
 
 from . import bam_header, ingest, multi
 from ._lib import (FSLR_MAX_L, FSLR_THR_ZERO_ALN, SCORE_EDGE, SCORE_GATE, SCORE_ZD_GATE, SCORE_ZD_OVERLAP,
-                   Context)
+                   Context, FslrError)
 from .prep import (CSR, IntervalData, IntervalItem, build_csr, data_order, first_last_masks, fold_overlap_threshold,
                    group_span, has_long_reads, kept_data_rows, mask_keep, pass_table, remove_reads_csr, umax_table)
 
@@ -52,7 +52,7 @@ __all__ = ['IntervalItem', 'keep_fillings', 'rename_chromosomes', 'chrom_to_str'
            'calculate_overlap', 'overall_jaccard_similarity', 'different_lengths_or_alignments', 'PairScores',
            'PairMatching',
            'device_coverage', 'DeviceCoverage', 'ClusterTable', 'cluster_table', 'ClusterLoci',
-           'ClusterJunctions', 'ClusterPaths']
+           'ClusterJunctions', 'ClusterPaths', 'ClusterPathSegments']
 
 
 class EdgeCapWarning(UserWarning):
@@ -656,6 +656,55 @@ class ClusterPaths:
                           np.int64)
 
 
+class ClusterPathSegments:
+    """DeviceIntervalIndex.cluster_path_segments' result (fslr_cluster_path_segments): per piece of every row of
+    ``paths`` (the ClusterPaths it was made on; slot ``tok_off[row] + piece``) the minimum, lower median and
+    maximum of the reference start and end of the piece in the reads that walk this path, and per link between a
+    piece and the next the same of the query-space gap (next piece's query start minus this piece's query end in
+    the read's own order: negative = overlap / microhomology, positive = inserted sequence).  A row's last piece
+    holds gap 0, 0, 0; without ``qend`` every gap is 0.  Nine int32 columns of ``n_tokens`` each."""
+
+    NAMES = ('start_min', 'start_med', 'start_max', 'end_min', 'end_med', 'end_max', 'gap_min', 'gap_med', 'gap_max')
+
+    def __init__(self, paths, start_min, start_med, start_max, end_min, end_med, end_max, gap_min, gap_med, gap_max):
+        self.paths = paths
+        self.start_min, self.start_med, self.start_max = start_min, start_med, start_max
+        self.end_min, self.end_med, self.end_max = end_min, end_med, end_max
+        self.gap_min, self.gap_med, self.gap_max = gap_min, gap_med, gap_max
+
+    def __len__(self):
+        return int(self.start_med.shape[0])
+
+    def columns(self):
+        """The nine columns in NAMES' order."""
+        return tuple(getattr(self, k) for k in self.NAMES)
+
+    def to_frame(self):
+        """One line per piece: ``cluster, path`` (0-based within its cluster), ``piece`` (0-based within its path),
+        ``chrom, start, end`` (the medians), ``strand`` ('-' for a reversed piece), ``n_reads`` of the path, then
+        ``start_min, start_max, end_min, end_max, gap_min, gap, gap_max`` (gap = the median)."""
+        p = self.paths
+        n_pieces = np.diff(p.tok_off)
+        row = np.repeat(np.arange(len(p), dtype=np.int64), n_pieces)
+        piece = np.arange(len(self), dtype=np.int64) - np.repeat(p.tok_off[:-1], n_pieces)
+        strand = np.where(p.rev == 0, '+', '-').astype(object)
+        return pd.DataFrame({'cluster': p.cluster_of_row()[row], 'path': p._path_in_cluster()[row], 'piece': piece,
+                             'chrom': np.asarray(p.loci.chrom)[p.locus], 'start': self.start_med, 'end': self.end_med,
+                             'strand': strand, 'n_reads': p.n_reads[row],
+                             'start_min': self.start_min, 'start_max': self.start_max,
+                             'end_min': self.end_min, 'end_max': self.end_max,
+                             'gap_min': self.gap_min, 'gap': self.gap_med, 'gap_max': self.gap_max})
+
+    def structure(self, row) -> str:
+        """The path of global row ``row`` as ClusterPaths.to_frame writes it, ``chrom:start-end:+`` per piece joined
+        by ``,``, with the consensus (median) coordinates of the piece in place of the locus' span."""
+        p = self.paths
+        a, b = int(p.tok_off[row]), int(p.tok_off[row + 1])
+        ch = np.asarray(p.loci.chrom)[p.locus[a:b]].tolist()
+        return ','.join(f'{c}:{s}-{e}:' + '-+'[r == 0] for c, s, e, r in
+                        zip(ch, self.start_med[a:b].tolist(), self.end_med[a:b].tolist(), p.rev[a:b].tolist()))
+
+
 def _rev_bits(strand) -> np.ndarray:
     """uint8 0/1 of a strand column given as booleans, 0/1 or '+' / '-' ('-' and true values are 1)."""
     s = np.asarray(strand)
@@ -1192,7 +1241,46 @@ class DeviceIntervalIndex:
         qkey, rev, loci = self._chain_inputs('cluster_paths', qstart, strand, G_or_labels)
         qn = getattr(self.data, 'qnames', None)
         code = np.asarray(self.csr.read_qcode)
-        return ClusterPaths(*self.ctx.cluster_paths(qkey, rev), loci, code if qn is None else np.asarray(qn[code]))
+        paths = ClusterPaths(*self.ctx.cluster_paths(qkey, rev), loci, code if qn is None else np.asarray(qn[code]))
+        # what cluster_path_segments may reuse: the rows, the table they were made on and the columns they were made with
+        self._paths_made = (getattr(self.ctx, '_cluster_info', None), qkey, rev, paths)
+        return paths
+
+    def cluster_path_segments(self, qstart, qend=None, strand=None, G_or_labels=None) -> ClusterPathSegments:
+        """Consensus coordinates and junction gaps per piece of every cluster path (fslr_cluster_path_segments): where
+        each piece lies in the reads that walk the path (min, lower median, max of start and end) and, with
+        ``qend``, the query-space gap the reads leave between a piece and the next.  ``qstart``, ``qend`` and
+        ``strand`` are aligned with the ``data`` list, as for cluster_paths; ``G_or_labels`` makes the cluster table
+        first.  The table's loci and paths are made when needed; the path rows this index made with the same
+        ``qstart`` and ``strand`` since its last table are reused.  An index with reads of more than 64 intervals
+        raises NotImplementedError.  The result holds its ClusterPaths as ``.paths``."""
+        if self.long is not None:
+            raise NotImplementedError(f'cluster_path_segments does not take an index with reads of more than '
+                                      f'{FSLR_MAX_L} intervals')
+        n = int(self.csr.n_intervals)
+        qe = None
+        if qend is not None:
+            e = np.asarray(qend)
+            if e.shape != (n,):
+                raise ValueError(f'qend holds {e.shape} values, the data list {n} intervals')
+            if e.dtype.kind not in 'iu' or (e.size and (e.min() < -(1 << 31) or e.max() >= (1 << 31))):
+                raise ValueError('qend must hold int32 values')
+            qe = e[np.asarray(self.csr.data_pos, np.int64)].astype(np.int32)
+        made = self.__dict__.get('_paths_made')
+        if G_or_labels is None and made is not None and made[0] is not None and \
+                made[0] is getattr(self.ctx, '_cluster_info', None):
+            q = np.asarray(qstart)
+            rev = None if strand is None else _rev_bits(strand)
+            pos = np.asarray(self.csr.data_pos, np.int64)
+            if q.shape == (n,) and q.dtype.kind in 'iu' and np.array_equal(q[pos], made[1]) and \
+                    (rev is None) == (made[2] is None) and (rev is None or (rev.shape == (n,) and np.array_equal(rev[pos], made[2]))):
+                try:
+                    return ClusterPathSegments(made[3], *self.ctx.cluster_path_segments(made[1], qe))
+                except FslrError as err:                 # the rows were dropped since (cluster_loci again): make them
+                    if 'no cluster paths' not in str(err):
+                        raise
+        paths = self.cluster_paths(qstart, strand, G_or_labels)
+        return ClusterPathSegments(paths, *self.ctx.cluster_path_segments(self._paths_made[1], qe))
 
     def __getitem__(self, chrom):
         return ChromosomeView(self, chrom)
@@ -1345,6 +1433,11 @@ class MultiGpuIndex:
         raise NotImplementedError('a multi-GPU index lives in the rank processes and cannot give cluster paths from '
                                   'here (fslr_cluster_paths needs the whole index on one context); build it with '
                                   'n_gpus=1')
+
+    def cluster_path_segments(self, *args, **kwargs):
+        raise NotImplementedError('a multi-GPU index lives in the rank processes and cannot give path segments from '
+                                  'here (fslr_cluster_path_segments needs the whole index on one context); build it '
+                                  'with n_gpus=1')
 
     def cluster_junctions_any(self, *args, **kwargs):
         return self.cluster_junctions(*args, **kwargs)

@@ -233,6 +233,7 @@ void fslr_ctx_destroy(fslr_ctx* c) {
   fslr_loci_free(c);
   fslr_junctions_free(c);
   fslr_paths_free(c);
+  fslr_segments_free(c);
   fslr_match_free(c);
   fslr_append_free(c);
   fslr_remove_free(c);

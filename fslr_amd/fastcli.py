@@ -257,6 +257,11 @@ def _run(args, basename, tsv, ints, strs, t, pool, ctx_f, state):
         write_cluster_paths(f'{basename}.mappings.cluster_paths.bed', f'{basename}.mappings.bed', trees,
                             None if dctx is not None or args.get('cluster_loci') or args.get('cluster_junctions') else g,
                             cmap, bool(args.get('cluster_long_reads')))
+    if args.get('cluster_path_segments'):
+        from .main import write_cluster_path_segments
+        write_cluster_path_segments(f'{basename}.mappings.cluster_path_segments.bed', f'{basename}.mappings.bed', trees,
+                                    None if dctx is not None or args.get('cluster_loci') or args.get('cluster_junctions') or
+                                    args.get('cluster_paths') else g, cmap)
     t['write'] = time.perf_counter() - t3
     # the device buffers go now (the caller's process would free them at exit anyway)
     t5 = time.perf_counter()

@@ -118,6 +118,11 @@ def assign_clusters(bed_file: pd.DataFrame, G: cluster.ClusterGraph, ctx=None):
 @click.option('--cluster-paths', required=False, is_flag=True,
               help='Also write {name}.mappings.cluster_paths.bed: per cluster its distinct read structures, the chain '
                    'of pieces each read walks, with the reads that agree on each (one GPU)')
+@click.option('--cluster-path-segments', required=False, is_flag=True,
+              help='Also write {name}.mappings.cluster_path_segments.bed: per piece of every cluster path its consensus '
+                   '(median) coordinates with their extrema over the reads that walk the path, and the query-space gap '
+                   'to the next piece (negative: overlap, positive: inserted sequence); loads as BED (one GPU; an '
+                   'input with reads of more than 64 intervals prints a notice and writes no file)')
 @click.option('--cluster-long-reads', required=False, is_flag=True,
               help='With --cluster-junctions / --cluster-paths: also take inputs that hold reads of more than 64 '
                    'intervals (up to 4096; fslr_cluster_junctions_any / fslr_cluster_paths_any) instead of printing a '
@@ -145,6 +150,8 @@ def pipeline(**args):
         raise click.UsageError('--cluster-junctions needs the whole index on one device: run it with --gpus 1')
     if args.get('cluster_paths') and (args.get('gpus') or 1) > 1:
         raise click.UsageError('--cluster-paths needs the whole index on one device: run it with --gpus 1')
+    if args.get('cluster_path_segments') and (args.get('gpus') or 1) > 1:
+        raise click.UsageError('--cluster-path-segments needs the whole index on one device: run it with --gpus 1')
     if not os.path.exists(args['out']):
         os.mkdir(args['out'])
     if not args['skip_alignment']:
@@ -252,21 +259,22 @@ JUNCTION_COLUMNS = ('cluster', 'chrom_a', 'side_a', 'locus_a', 'bp_a_min', 'bp_a
                     'bp_b_min', 'bp_b_max', 'n_obs', 'n_reads')
 
 
-def junction_inputs(path, rows):
-    """``(qstart, rev)`` of the .mappings.bed rows ``rows`` (file row numbers: ``data.index``) from a narrow read
-    of ``path``.  ``qstart`` is already in the frame of the read's primary alignment, so an interval runs against
+def junction_inputs(path, rows, with_qend=False):
+    """``(qstart, rev)``, with ``with_qend`` ``(qstart, rev, qend)``, of the .mappings.bed rows ``rows`` (file row
+    numbers: ``data.index``) from a narrow read of ``path``.  ``qstart`` is already in the frame of the read's primary alignment, so an interval runs against
     the query order iff its strand differs from the primary row's: rev = (strand == '-') xor (the primary row's
     strand == '-').  The primary row is the read's first row with a non-empty ``seq`` (it may be one of the two
     end rows that clustering drops); a read without one counts as forward."""
-    bed = pd.read_csv(path, sep='\t', usecols=['qname', 'qstart', 'strand', 'seq'], dtype={'seq': str, 'strand': str},
-                      na_filter=False)
+    bed = pd.read_csv(path, sep='\t', usecols=['qname', 'qstart', 'strand', 'seq'] + (['qend'] if with_qend else []),
+                      dtype={'seq': str, 'strand': str}, na_filter=False)
     codes, uniq = pd.factorize(bed['qname'], sort=False)
     neg = (bed['strand'] == '-').to_numpy()
     prim = np.flatnonzero((bed['seq'] != '').to_numpy())[::-1]        # descending: a read's first row is written last
     prim_neg = np.zeros(len(uniq), bool)
     prim_neg[codes[prim]] = neg[prim]
     rows = np.asarray(rows, np.int64)
-    return bed['qstart'].to_numpy()[rows], (neg ^ prim_neg[codes])[rows].astype(np.uint8)
+    out = (bed['qstart'].to_numpy()[rows], (neg ^ prim_neg[codes])[rows].astype(np.uint8))
+    return out + (bed['qend'].to_numpy()[rows],) if with_qend else out
 
 
 def write_cluster_junctions(path, bed_path, trees, G_or_labels, chrom_to_num_map, long_reads=False):
@@ -303,6 +311,27 @@ def write_cluster_paths(path, bed_path, trees, G_or_labels, chrom_to_num_map, lo
     name_of = {v: k for k, v in chrom_to_num_map.items()}
     paths.loci.chrom = np.asarray([name_of[c] for c in paths.loci.chrom.tolist()], dtype=object)
     paths.to_frame()[list(PATH_COLUMNS)].to_csv(path, sep='\t', index=False)
+    return True
+
+
+SEGMENT_COLUMNS = ('chrom', 'start', 'end', 'cluster', 'path', 'piece', 'strand', 'n_reads', 'start_min', 'start_max',
+                   'end_min', 'end_max', 'gap_min', 'gap', 'gap_max')
+
+
+def write_cluster_path_segments(path, bed_path, trees, G_or_labels, chrom_to_num_map):
+    """--cluster-path-segments: one line per piece of every cluster path (cluster.ClusterPathSegments.to_frame) as a
+    tab-separated file with SEGMENT_COLUMNS: chrom, median start and median end first, so it loads as BED;
+    chromosome names as in the input.  An index with reads of more than 64 intervals prints a notice and writes
+    nothing (--cluster-long-reads does not lift this)."""
+    if getattr(trees, 'long', None) is not None:
+        print('--cluster-path-segments: the input holds reads of more than 64 intervals; no path segments file is '
+              'written.')
+        return False
+    qstart, rev, qend = junction_inputs(bed_path, trees.data.index, with_qend=True)
+    frame = trees.cluster_path_segments(qstart, qend, rev, G_or_labels).to_frame()
+    name_of = {v: k for k, v in chrom_to_num_map.items()}
+    frame['chrom'] = [name_of.get(c, c) for c in frame['chrom'].tolist()]      # (--cluster-paths named its rows' loci)
+    frame[list(SEGMENT_COLUMNS)].to_csv(path, sep='\t', index=False)
     return True
 
 
@@ -372,6 +401,11 @@ def _cluster_and_write(args, basename, bed_file, tsv, t):
         write_cluster_paths(f'{basename}.mappings.cluster_paths.bed', f'{basename}.mappings.bed', interval_tree,
                             None if args.get('cluster_loci') or args.get('cluster_junctions') else network,
                             chrom_to_num_map, bool(args.get('cluster_long_reads')))
+    if args.get('cluster_path_segments'):
+        write_cluster_path_segments(f'{basename}.mappings.cluster_path_segments.bed', f'{basename}.mappings.bed',
+                                    interval_tree,
+                                    None if args.get('cluster_loci') or args.get('cluster_junctions') or
+                                    args.get('cluster_paths') else network, chrom_to_num_map)
     t['write'] = time.perf_counter() - t3
     if args.get('timings'):
         st = network.stats

@@ -836,6 +836,51 @@ int  fslr_cluster_paths_timings(fslr_ctx *ctx, float *ms);
 int  fslr_cluster_junctions_any(fslr_ctx *ctx, const int32_t *iv_qkey, const uint8_t *iv_rev, int64_t n_intervals, int64_t *n_rows);
 int  fslr_cluster_paths_any(fslr_ctx *ctx, const int32_t *iv_qkey, const uint8_t *iv_rev, int64_t n_intervals, int64_t *n_rows, int64_t *n_tokens);
 
+/* Path segments: for every piece (token slot) of every cluster path, where the piece lies in the reads that walk
+ * this path (a locus is the merged span of ALL the cluster's reads on that chromosome, not the piece's extent),
+ * and for every link between two consecutive pieces the query-space gap the reads leave there.  On top of what
+ * fslr_cluster_paths needs plus the resident path rows of the current table.
+ *   Inputs: iv_qkey[n_intervals], the column the paths were made with (the query start), and iv_qend[n_intervals]
+ *   (the query end; may be NULL: no gaps are computed and the three gap columns are all 0); caller-owned host
+ *   arrays in CSR interval order.  The strand column is not needed: flipped is resident.
+ *   Chain, as for the paths: a clustered read's resident intervals ordered by (iv_qkey ascending, CSR position
+ *   ascending on equal keys).  The interval at chain rank t of a read r of L intervals has canonical position
+ *   p = flipped[r] ? L - 1 - t : t and lands in token slot s = tok_off[path_of_read[r]] + p, 0 <= s < n_tokens.
+ *   L equals the row's length, so s always lies in the read's own row, whatever column the caller passes: a
+ *   different iv_qkey gives this contract's answer for that column's order, never an out-of-range slot.
+ *   Per slot, over the k = n_reads[row] intervals that land in it (one per read of the row), six int32 columns:
+ *   start_min, start_med, start_max and end_min, end_med, end_max of the intervals' reference start and end.  The
+ *   median is the lower median: with the values ascending, element (k - 1) / 2.
+ *   Per link: a link joins slots s and s + 1 of one row and is stored at s.  The gap of a read there is iv_qkey
+ *   of the later interval in the read's OWN chain order minus iv_qend of the earlier one, computed in 64 bits and
+ *   saturated to int32: the same number whichever direction the read walks the path.  Negative: the two pieces
+ *   overlap on the query (microhomology); positive: inserted sequence.  Columns gap_min, gap_med, gap_max; the
+ *   last slot of every row holds 0, 0, 0.
+ *   The bytes are the same on every run.
+ * fslr_cluster_path_segments: computes the rows and keeps them resident (*n_tokens, may be NULL); syncs.
+ *   FSLR_ERR_STATE, named in the message: those of fslr_cluster_paths (no reads set; no index built, or a partial
+ *   one; no cluster table; a table whose n differs from the context's real read count; no loci rows of this
+ *   table), and no resident path rows of this table (fslr_cluster_paths first).  FSLR_ERR_INVALID: iv_qkey NULL;
+ *   n_intervals different from the context's; a context with virtual reads (reads of more than FSLR_MAX_L
+ *   intervals are out of scope here); more than 2^30 intervals.  A failed call keeps the previous segment rows, a
+ *   successful one replaces them; whatever drops or replaces the path rows (fslr_cluster_table, a successful
+ *   fslr_cluster_loci, a successful fslr_cluster_paths / fslr_cluster_paths_any) drops them; fslr_ctx_destroy
+ *   frees them.  The path, junction and loci rows, the query state and everything else are left alone.
+ *   The selection runs in three tiers by k: 2..S in a lane group (counting by shuffles), S+1..T sorted in LDS by
+ *   one workgroup, above T an exact radix select by one workgroup; k == 1 is written as it is met.  The
+ *   environment variables FSLR_SEGS_SMALL (S, 1..64, default 64) and FSLR_SEGS_LDS (T, S..4096, default 4096) are
+ *   read per call and change no result.
+ * fslr_get_cluster_path_segments: D2H of the rows (NULL outputs are skipped): start, end, gap, each
+ *   [3 x n_tokens] = the columns min, med, max one after another.  FSLR_ERR_STATE without rows, FSLR_ERR_INVALID
+ *   when token_capacity < n_tokens (nothing is written).
+ * fslr_cluster_path_segments_timings (fslr_set_profiling 1 or 2): HIP-event time (ms[0]) of the last
+ *   fslr_cluster_path_segments, from the end of the columns' upload to the last operation on the stream;
+ *   FSLR_ERR_STATE when it was not profiled. */
+int  fslr_cluster_path_segments(fslr_ctx *ctx, const int32_t *iv_qkey, const int32_t *iv_qend, int64_t n_intervals, int64_t *n_tokens);
+int  fslr_get_cluster_path_segments(fslr_ctx *ctx, int32_t *start /* [3 x n_tokens]: min, med, max */, int32_t *end, int32_t *gap,
+                                    int64_t token_capacity);
+int  fslr_cluster_path_segments_timings(fslr_ctx *ctx, float *ms);
+
 /* Match reads that are NOT in the uploaded set against the resident index: for a query read Q, given
  * like a row of fslr_reads (its intervals in the order its loop walks them, dense chromosome ids of the
  * uploaded CSR, folded iv_thr, its qlen2 and n_alignments), what the reference's pair loop
