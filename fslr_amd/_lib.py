@@ -56,7 +56,8 @@ EXPORTED = ['fslr_abi_version', 'fslr_last_error', 'fslr_ctx_create', 'fslr_ctx_
             'fslr_cluster_junctions', 'fslr_get_cluster_junctions', 'fslr_cluster_junctions_timings',
             'fslr_cluster_paths', 'fslr_get_cluster_paths', 'fslr_cluster_paths_timings',
             'fslr_cluster_junctions_any', 'fslr_cluster_paths_any',
-            'fslr_cluster_path_segments', 'fslr_get_cluster_path_segments', 'fslr_cluster_path_segments_timings']
+            'fslr_cluster_path_segments', 'fslr_get_cluster_path_segments', 'fslr_cluster_path_segments_timings',
+            'fslr_cluster_path_segments_any']
 # fslr_score_pairs' flag bits (include/fslr_hip.h)
 SCORE_GATE, SCORE_EDGE, SCORE_ZD_GATE, SCORE_ZD_OVERLAP = 1, 2, 4, 8
 # fslr_coverage_*: keys per tile of the sorted arrays, queries per chunk (include/fslr_hip.h)
@@ -286,6 +287,7 @@ def load(path: str = LIB_PATH):
         'fslr_cluster_junctions_any': (ctypes.c_int, [vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int64)]),
         'fslr_cluster_paths_any': (ctypes.c_int, [vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
         'fslr_cluster_path_segments': (ctypes.c_int, [vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int64)]),
+        'fslr_cluster_path_segments_any': (ctypes.c_int, [vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int64)]),
         'fslr_get_cluster_path_segments': (ctypes.c_int, [vp, vp, vp, vp, i64]),
         'fslr_cluster_path_segments_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
     }
@@ -1474,6 +1476,15 @@ class Context:
         Returns nine int32 columns of n_tokens each, in the slots' order (``tok_off`` of cluster_paths):
         ``(start_min, start_med, start_max, end_min, end_med, end_max, gap_min, gap_med, gap_max)``; the medians are
         lower medians, a gap is stored at the earlier of the two slots it joins and a row's last slot holds 0."""
+        return self._cluster_path_segments('fslr_cluster_path_segments', qkey, qend)
+
+    def cluster_path_segments_any(self, qkey, qend=None):
+        """cluster_path_segments for a context that holds reads of more than 64 intervals
+        (fslr_cluster_path_segments_any; cluster_paths_any first): ``qkey`` and ``qend`` per interval of the real CSR,
+        in its order.  On a context without such reads it is cluster_path_segments, byte for byte."""
+        return self._cluster_path_segments('fslr_cluster_path_segments_any', qkey, qend)
+
+    def _cluster_path_segments(self, name, qkey, qend):
         qkey = np.ascontiguousarray(qkey, dtype=np.int32)
         if qkey.ndim != 1:
             raise ValueError('qkey must be one-dimensional')
@@ -1483,7 +1494,7 @@ class Context:
                 raise ValueError('qend must have qkey\'s shape')
         nt = ctypes.c_int64(0)
         # (an empty array still passes an address: NULL keys are an error of their own)
-        self._check(self._L.fslr_cluster_path_segments(
+        self._check(getattr(self._L, name)(
             self._h, _ptr(qkey) if qkey.size else _ptr(np.zeros(1, np.int32)),
             None if qend is None else _ptr(qend) if qend.size else _ptr(np.zeros(1, np.int32)), int(qkey.size), ctypes.byref(nt)))
         nt = int(nt.value)

@@ -1229,7 +1229,9 @@ class DeviceIntervalIndex:
         qkey, rev, loci = self._chain_inputs('cluster_paths_any', qstart, strand, G_or_labels, True)
         qn = getattr(self.data, 'qnames', None)
         code = np.asarray(self.csr.read_qcode)
-        return ClusterPaths(*self.ctx.cluster_paths_any(qkey, rev), loci, code if qn is None else np.asarray(qn[code]))
+        paths = ClusterPaths(*self.ctx.cluster_paths_any(qkey, rev), loci, code if qn is None else np.asarray(qn[code]))
+        self._paths_made = (getattr(self.ctx, '_cluster_info', None), qkey, rev, paths)     # (see cluster_paths)
+        return paths
 
     def cluster_paths(self, qstart, strand=None, G_or_labels=None) -> ClusterPaths:
         """The distinct read structures of each cluster and how many reads agree on each (fslr_cluster_paths).  A
@@ -1257,6 +1259,19 @@ class DeviceIntervalIndex:
         if self.long is not None:
             raise NotImplementedError(f'cluster_path_segments does not take an index with reads of more than '
                                       f'{FSLR_MAX_L} intervals')
+        return self._path_segments(False, qstart, qend, strand, G_or_labels)
+
+    def cluster_path_segments_any(self, qstart, qend=None, strand=None, G_or_labels=None) -> ClusterPathSegments:
+        """cluster_path_segments for an index that may hold reads of more than 64 intervals, up to 4096
+        (fslr_cluster_path_segments_any): a long read's pieces and gaps run over all its intervals.  The arguments,
+        the reuse of resident path rows and the result are cluster_path_segments'; the loci and the paths are made
+        through cluster_loci / cluster_paths_any, the rules for ``G_or_labels`` are cluster_junctions_any's.  On an
+        index without long reads it returns what cluster_path_segments returns."""
+        return self._path_segments(True, qstart, qend, strand, G_or_labels)
+
+    def _path_segments(self, any_length, qstart, qend, strand, G_or_labels):
+        make_paths = self.cluster_paths_any if any_length else self.cluster_paths
+        segments = self.ctx.cluster_path_segments_any if any_length else self.ctx.cluster_path_segments
         n = int(self.csr.n_intervals)
         qe = None
         if qend is not None:
@@ -1275,12 +1290,12 @@ class DeviceIntervalIndex:
             if q.shape == (n,) and q.dtype.kind in 'iu' and np.array_equal(q[pos], made[1]) and \
                     (rev is None) == (made[2] is None) and (rev is None or (rev.shape == (n,) and np.array_equal(rev[pos], made[2]))):
                 try:
-                    return ClusterPathSegments(made[3], *self.ctx.cluster_path_segments(made[1], qe))
+                    return ClusterPathSegments(made[3], *segments(made[1], qe))
                 except FslrError as err:                 # the rows were dropped since (cluster_loci again): make them
                     if 'no cluster paths' not in str(err):
                         raise
-        paths = self.cluster_paths(qstart, strand, G_or_labels)
-        return ClusterPathSegments(paths, *self.ctx.cluster_path_segments(self._paths_made[1], qe))
+        paths = make_paths(qstart, strand, G_or_labels)
+        return ClusterPathSegments(paths, *segments(self._paths_made[1], qe))
 
     def __getitem__(self, chrom):
         return ChromosomeView(self, chrom)
@@ -1444,6 +1459,9 @@ class MultiGpuIndex:
 
     def cluster_paths_any(self, *args, **kwargs):
         return self.cluster_paths(*args, **kwargs)
+
+    def cluster_path_segments_any(self, *args, **kwargs):
+        return self.cluster_path_segments(*args, **kwargs)
 
 
 def _open_context(device: int | None = None) -> Context:

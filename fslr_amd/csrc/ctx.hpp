@@ -1,6 +1,7 @@
 // ctx.hpp — the context behind the C ABI's opaque fslr_ctx (internal to libfslr_hip.so):
 // HBM buffers, stream, the last query's parameters, error text.  Shared by capi.hip and cap.hip.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -321,6 +322,22 @@ int dalloc(fslr_ctx* c, T** p, size_t count) {
   if (count == 0) count = 1;
   hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
   if (e != hipSuccess) return fail(c, FSLR_ERR_NOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+  return FSLR_OK;
+}
+
+// host -> device through a pinned chunk of stage_bytes, for a column the caller gives in the real CSR's order on a
+// context whose intervals were permuted (fslr_set_reads_any): virtual interval k takes src[perm[k]]; each chunk
+// syncs (the chunk is reused).  The _any calls of junctions.hip, paths.hip and segments.hip stage through it.
+template <typename T>
+int up_perm(fslr_ctx* c, unsigned char* stage_buf, size_t stage_bytes, T* dst, const T* src, const std::vector<int>& perm) {
+  const size_t per = stage_bytes / sizeof(T), n = perm.size();
+  T* stage = reinterpret_cast<T*>(stage_buf);
+  for (size_t at = 0; at < n; at += per) {
+    const size_t m = std::min(per, n - at);
+    for (size_t k = 0; k < m; ++k) stage[k] = src[perm[at + k]];
+    HIP_TRY(c, hipMemcpyAsync(dst + at, stage, m * sizeof(T), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
   return FSLR_OK;
 }
 

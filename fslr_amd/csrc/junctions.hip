@@ -421,21 +421,6 @@ int up(fslr_ctx* c, JunctionWork* w, void* dst, const void* src, size_t bytes) {
   return FSLR_OK;
 }
 
-// the same for a column the caller gives in the real CSR's order on a context whose intervals were permuted
-// (fslr_set_reads_any): virtual interval k takes src[perm[k]]
-template <typename T>
-int up_perm(fslr_ctx* c, JunctionWork* w, T* dst, const T* src, const std::vector<int>& perm) {
-  const size_t per = kStageBytes / sizeof(T), n = perm.size();
-  T* stage = reinterpret_cast<T*>(w->stage);
-  for (size_t at = 0; at < n; at += per) {
-    const size_t m = std::min(per, n - at);
-    for (size_t k = 0; k < m; ++k) stage[k] = src[perm[at + k]];
-    HIP_TRY(c, hipMemcpyAsync(dst + at, stage, m * sizeof(T), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  return FSLR_OK;
-}
-
 int read_last(fslr_ctx* c, JunctionWork* w, const int* a, const int* b, int64_t last, int64_t* out) {
   k_jn_last<<<1, 64, 0, c->stream>>>(a, b, last, w->info);
   HIP_TRY(c, hipGetLastError());
@@ -533,9 +518,9 @@ int junctions_run(fslr_ctx* c, const int32_t* iv_qkey, const uint8_t* iv_rev, in
   w->timed = false;
   w->ms = 0;
   if (virt && !c->lg_perm.empty()) {                // the caller's order is the real CSR's
-    if ((rc = up_perm(c, w, w->qkey, iv_qkey, c->lg_perm))) return rc;
+    if ((rc = up_perm(c, w->stage, kStageBytes, w->qkey, iv_qkey, c->lg_perm))) return rc;
     if (iv_rev)
-      if ((rc = up_perm(c, w, w->rev, iv_rev, c->lg_perm))) return rc;
+      if ((rc = up_perm(c, w->stage, kStageBytes, w->rev, iv_rev, c->lg_perm))) return rc;
   } else {
     if ((rc = up(c, w, w->qkey, iv_qkey, static_cast<size_t>(ni) * sizeof(int)))) return rc;
     if (iv_rev)

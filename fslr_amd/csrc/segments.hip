@@ -15,6 +15,13 @@
 //                   shuffles, the next piece's key through LDS by rank; the value of (row, position p, ordinal o)
 //                   goes to base[row] + p * k + o of its stream; a row of one read writes min = med = max to
 //                   the output; the read of ordinal 0 writes k, the bucket's first word and "last slot" per slot
+//   fslr_cluster_path_segments_any on virtual reads: k_chain_long_flag on path_of_read, a hipcub scan and
+//                   k_chain_long_compact list the clustered reads of more than FSLR_MAX_L intervals (their count
+//                   comes back with the bucket words'), and when there are any
+//   k_seg_emit_long one workgroup per such read: chain.hpp's bitonic sort of the chain words in LDS, the thread at
+//                   rank t takes its interval from the word's low bits and the next piece's key from word t + 1,
+//                   and writes what k_seg_emit's lane writes.  A row's reads share its length, so one of the two
+//                   kernels serves a row wholly
 //   k_seg_flags     per slot: which tier its k falls in
 //   hipcub select   the slots of each tier, ascending (three Flagged selections of a counting iterator)
 //   k_seg_small     2 <= k <= S: a lane group of 16 / 32 / 64 per (slot, stream); each lane counts the smaller and
@@ -56,6 +63,10 @@ struct SegmentWork {
   // per read: sort keys in / out, reads in / out, ord
   unsigned* rbuf = nullptr;          // [5 x rcap]
   int64_t rcap = 0;
+  // fslr_cluster_path_segments_any on virtual reads: flag, pos and the list of the clustered reads of more than
+  // FSLR_MAX_L intervals
+  int* lbuf = nullptr;               // [3 x (lcap + 1)]
+  int64_t lcap = 0;
   // per row: n_reads and their scan; len * k and their scan
   int* wbuf = nullptr;               // [2 x (wcap + 1)]
   long long* wbuf64 = nullptr;       // [2 x (wcap + 1)]
@@ -103,7 +114,7 @@ void fslr_segments_free(fslr_ctx* c) {
   SegmentWork* w = c->sgw;
   if (!w) return;
   dfree(w->out), dfree(w->qkey), dfree(w->qend), dfree(w->rbuf), dfree(w->wbuf), dfree(w->wbuf64), dfree(w->tbuf);
-  dfree(w->tbuf64), dfree(w->tbuf8), dfree(w->vbuf), dfree(w->cnt), dfree(w->temp);
+  dfree(w->tbuf64), dfree(w->tbuf8), dfree(w->vbuf), dfree(w->cnt), dfree(w->temp), dfree(w->lbuf);
   if (w->host) (void)hipHostFree(w->host);
   if (w->stage) (void)hipHostFree(w->stage);
   if (w->ev_ok)
@@ -156,7 +167,9 @@ __global__ __launch_bounds__(kBlock) void k_seg_ord(const unsigned* __restrict__
 
 // ---- emit ---------------------------------------------------------------------------------------
 struct EmitArgs {
-  const int4* rmeta;
+  RealReads rr;                      // the real lists on a context with virtual reads (n = the real reads)
+  const int* longs;                  // [n_long] the reads of k_seg_emit_long
+  long long n_long;
   const int4* iv;                    // {chrom, start, end, thr}
   const int *qkey, *qend;            // qend null: no gaps
   const int* por;
@@ -175,36 +188,85 @@ __device__ __forceinline__ int sat32(long long v) {
   return static_cast<int>(max(static_cast<long long>(INT_MIN), min(static_cast<long long>(INT_MAX), v)));
 }
 
+__device__ __forceinline__ int unbias(unsigned u) { return static_cast<int>(u ^ 0x80000000u); }
+
+// a clustered read as the emit kernels see it: len == 0 when it writes nothing
+struct EmitRead {
+  int len = 0, first = 0, k = 0, o = 0, flip = 0;
+  long long t0 = 0, b0 = 0;
+};
+
+// read r of `len` intervals (the caller checked it against its kernel's range): its row, ordinal and bucket
+__device__ __forceinline__ EmitRead emit_read(const EmitArgs& a, long long r, int first, int len) {
+  EmitRead e;
+  e.first = first;
+  const int row = a.por[r];
+  if (row < 0 || row >= a.n_rows) return e;
+  e.t0 = a.tok_off[row];
+  e.k = a.nreads[row];
+  e.o = a.ord[r];
+  e.b0 = a.base[row];
+  e.flip = a.flipped[r] != 0;
+  // a read's row has the read's length and holds its ordinal, so every slot below lies in the row
+  if (a.tok_off[row + 1] - e.t0 == len && e.o >= 0 && e.o < e.k) e.len = len;
+  return e;
+}
+
+// the interval at chain rank `rank` of read e: record rec, and with link (a next piece exists and the caller
+// brought the query ends) the gap to that piece
+__device__ __forceinline__ void emit_piece(const EmitArgs& a, const EmitRead& e, int rank, const int4& rec, bool link, int gap) {
+  const int len = e.len, k = e.k, o = e.o;
+  const long long t0 = e.t0, b0 = e.b0;
+  const int p = e.flip ? len - 1 - rank : rank;
+  const long long s = t0 + p;
+  FSLR_BOUND(s, a.nt);
+  // the link to the next piece of the read's own chain lies between positions p and p -+ 1: stored at the smaller
+  const int pl = e.flip ? len - 2 - rank : rank;
+  if (k == 1) {
+    a.out[s] = a.out[a.nt + s] = a.out[2 * a.nt + s] = rec.y;
+    a.out[3 * a.nt + s] = a.out[4 * a.nt + s] = a.out[5 * a.nt + s] = rec.z;
+    if (link) {
+      FSLR_BOUND(t0 + pl, a.nt);
+      a.out[6 * a.nt + t0 + pl] = a.out[7 * a.nt + t0 + pl] = a.out[8 * a.nt + t0 + pl] = gap;
+    }
+    a.slot_k[s] = 1;
+  } else {
+    const long long at = b0 + static_cast<long long>(p) * k + o;
+    FSLR_BOUND(at, a.n_vals);
+    a.vs[at] = rec.y;
+    a.ve[at] = rec.z;
+    if (link) {
+      FSLR_BOUND(b0 + static_cast<long long>(pl) * k + o, a.n_vals);
+      a.vg[b0 + static_cast<long long>(pl) * k + o] = gap;
+    }
+    if (o == 0) {                                   // one read per row describes its slots
+      a.slot_k[s] = k;
+      a.slot_base[s] = b0 + static_cast<long long>(p) * k;
+      a.slot_last[s] = static_cast<unsigned char>(p == len - 1);
+    }
+  }
+}
+
 // 64 / W reads side by side: read r (valid: it exists) on the W-lane group of this lane, interval j = the lane's
 // place in the group.  lds: this wavefront's 64 slots.
 template <int W>
 __device__ __forceinline__ void emit_group(const EmitArgs& a, long long r, bool valid, int lane, int* lds) {
   const int j = lane & (W - 1), gbase = lane & ~(W - 1);
-  int len = 0, first = 0, k = 0, o = 0, flip = 0;
-  long long t0 = 0, b0 = 0;
+  EmitRead e;
   if (valid) {
     FSLR_BOUND(r, a.n);
-    const int4 rm = a.rmeta[r];
-    first = rm.x;
-    len = rm.y & 0xFFFF;
-    const int row = a.por[r];
-    if (row < 0 || row >= a.n_rows || len > W) {    // len > W: the caller chose W for its reads
-      len = 0;
-    } else {
-      t0 = a.tok_off[row];
-      k = a.nreads[row];
-      o = a.ord[r];
-      b0 = a.base[row];
-      flip = a.flipped[r] != 0;
-      // a read's row has the read's length and holds its ordinal, so every slot below lies in the row
-      if (a.tok_off[row + 1] - t0 != len || o < 0 || o >= k) len = 0;
-    }
+    const int4 rm = a.rr.rmeta[r];
+    const int len = a.rr.len(r, rm);
+    // len > W: a real read of more than FSLR_MAX_L intervals (k_seg_emit_long's; its first chunk is not a read of
+    // its own); otherwise the caller chose W for its reads
+    if (len <= W) e = emit_read(a, r, rm.x, len);
   }
+  const int len = e.len;
   const bool have = j < len;
   int key = 0, qe = 0;
   int4 rec = make_int4(0, 0, 0, 0);
   if (have) {
-    const long long i = static_cast<long long>(first) + j;
+    const long long i = static_cast<long long>(e.first) + j;
     FSLR_BOUND(i, a.ni);
     rec = a.iv[i];
     key = a.qkey[i];
@@ -214,37 +276,10 @@ __device__ __forceinline__ void emit_group(const EmitArgs& a, long long r, bool 
   if (have) lds[gbase + rank] = key;                // rank < len <= W: the group's slots
   wave_lds_sync();
   if (have) {
-    const int p = flip ? len - 1 - rank : rank;
-    const long long s = t0 + p;
-    FSLR_BOUND(s, a.nt);
-    // the link to the next piece of the read's own chain lies between positions p and p -+ 1: stored at the smaller
     const bool link = a.qend && rank + 1 < len;
-    const int pl = flip ? len - 2 - rank : rank;
     int gap = 0;
     if (link) gap = sat32(static_cast<long long>(lds[gbase + rank + 1]) - static_cast<long long>(qe));
-    if (k == 1) {
-      a.out[s] = a.out[a.nt + s] = a.out[2 * a.nt + s] = rec.y;
-      a.out[3 * a.nt + s] = a.out[4 * a.nt + s] = a.out[5 * a.nt + s] = rec.z;
-      if (link) {
-        FSLR_BOUND(t0 + pl, a.nt);
-        a.out[6 * a.nt + t0 + pl] = a.out[7 * a.nt + t0 + pl] = a.out[8 * a.nt + t0 + pl] = gap;
-      }
-      a.slot_k[s] = 1;
-    } else {
-      const long long at = b0 + static_cast<long long>(p) * k + o;
-      FSLR_BOUND(at, a.n_vals);
-      a.vs[at] = rec.y;
-      a.ve[at] = rec.z;
-      if (link) {
-        FSLR_BOUND(b0 + static_cast<long long>(pl) * k + o, a.n_vals);
-        a.vg[b0 + static_cast<long long>(pl) * k + o] = gap;
-      }
-      if (o == 0) {                                 // one read per row describes its slots
-        a.slot_k[s] = k;
-        a.slot_base[s] = b0 + static_cast<long long>(p) * k;
-        a.slot_last[s] = static_cast<unsigned char>(p == len - 1);
-      }
-    }
+    emit_piece(a, e, rank, rec, link, gap);
   }
   wave_lds_sync();                                  // the next pass writes the slots again
 }
@@ -261,7 +296,7 @@ __global__ __launch_bounds__(kBlock) void k_seg_emit(EmitArgs a) {
     int len = 0;
     if (r16 < a.n) {
       FSLR_BOUND(r16, a.n);
-      len = a.rmeta[r16].y & 0xFFFF;
+      len = a.rr.len(r16, a.rr.rmeta[r16]);
       if (a.por[r16] < 0 || len > FSLR_MAX_L) len = 0;
     }
     const bool over16 = __ballot(len > 16) != 0ull, over32 = __ballot(len > 32) != 0ull;
@@ -276,6 +311,42 @@ __global__ __launch_bounds__(kBlock) void k_seg_emit(EmitArgs a) {
     } else {
       for (int p = 0; p < 4; ++p) emit_group<64>(a, r0 + p, r0 + p < a.n, lane, lds);
     }
+  }
+}
+
+// One workgroup per clustered read of more than FSLR_MAX_L intervals (a.longs): the chain order by an LDS sort;
+// the thread that holds rank t takes its interval's place in the list from the word's low bits and the next
+// piece's key from word t + 1, and writes what emit_group's lane writes.  32 KiB of LDS, no atomics.
+__global__ __launch_bounds__(kChainBlock) void k_seg_emit_long(EmitArgs a) {
+  __shared__ unsigned long long s_w[kChainMaxL];
+  for (long long q = blockIdx.x; q < a.n_long; q += gridDim.x) {
+    FSLR_BOUND(q, a.n_long);
+    const int r = a.longs[q];
+    FSLR_BOUND(r, a.n);
+    const int4 rm = a.rr.rmeta[r];
+    const int rlen = a.rr.len(r, rm), off2 = a.rr.second(r, rlen);
+    EmitRead e;
+    if (rlen > FSLR_MAX_L && rlen <= kChainMaxL) e = emit_read(a, r, rm.x, rlen);
+    const int len = min(e.len, kChainMaxL);         // bounds the LDS indices below
+    if (len == 0) continue;                         // block-uniform: no barrier is skipped by a part of the block
+    chain_sort_lds(s_w, a.qkey, e.first, off2, len, a.ni);
+    for (int t = threadIdx.x; t < len; t += kChainBlock) {
+      FSLR_BOUND(t, kChainMaxL);
+      const unsigned long long w = s_w[t];
+      const int j = static_cast<int>(w & (kChainMaxL - 1));
+      FSLR_BOUND(j, len);
+      const long long i = list_at(e.first, off2, j);
+      FSLR_BOUND(i, a.ni);
+      const int4 rec = a.iv[i];
+      const bool link = a.qend && t + 1 < len;
+      int gap = 0;
+      if (link) {
+        FSLR_BOUND(t + 1, kChainMaxL);
+        gap = sat32(static_cast<long long>(unbias(static_cast<unsigned>(s_w[t + 1] >> 12))) - static_cast<long long>(a.qend[i]));
+      }
+      emit_piece(a, e, t, rec, link, gap);
+    }
+    __syncthreads();                                // the next read writes the words again
   }
 }
 
@@ -376,8 +447,6 @@ __global__ __launch_bounds__(kBlock) void k_seg_small(SelArgs a) {
     }
   }
 }
-
-__device__ __forceinline__ int unbias(unsigned u) { return static_cast<int>(u ^ 0x80000000u); }
 
 // One workgroup per (slot, stream) of k <= kLdsMax values: chain_sort_lds' words are (biased value, place), so the
 // sorted words give elements 0, (k - 1) / 2 and k - 1.  32 KiB of LDS.
@@ -519,15 +588,13 @@ struct NewRows {
   ~NewRows() { dfree(out); }
 };
 
-}  // namespace
-
-extern "C" {
-
-int fslr_cluster_path_segments(fslr_ctx* c, const int32_t* iv_qkey, const int32_t* iv_qend, int64_t n_intervals,
-                               int64_t* n_tokens_out) {
+// fslr_cluster_path_segments (any = false: a context with virtual reads is refused) and
+// fslr_cluster_path_segments_any.  On a context without virtual reads the two run the same code.
+int segments_run(fslr_ctx* c, const int32_t* iv_qkey, const int32_t* iv_qend, int64_t n_intervals, int64_t* n_tokens_out,
+                 bool any) {
   if (!c) return FSLR_ERR_INVALID;
   if (!c->reads_set || c->n == 0) return fail(c, FSLR_ERR_STATE, "fslr_cluster_path_segments: no reads set");
-  if (int rc = search_state(c, "fslr_cluster_path_segments")) return rc;
+  if (int rc = search_state(c, any ? "fslr_cluster_path_segments_any" : "fslr_cluster_path_segments")) return rc;
   const int* cid = nullptr;
   int64_t tn = 0, nc = 0;
   if (!fslr_cluster_view(c, &cid, &tn, &nc))
@@ -546,14 +613,19 @@ int fslr_cluster_path_segments(fslr_ctx* c, const int32_t* iv_qkey, const int32_
   fslr_paths_rows pv;
   if (!fslr_paths_view(c, &pv) || pv.n_clusters != nc || pv.n != n_real)
     return fail(c, FSLR_ERR_STATE, "fslr_cluster_path_segments: no cluster paths of this table (fslr_cluster_paths first)");
-  if (c->lg_set)
+  if (c->lg_set && !any)
     return fail(c, FSLR_ERR_INVALID, "fslr_cluster_path_segments: the context holds reads of more than " +
                                          std::to_string(FSLR_MAX_L) + " intervals (out of scope here)");
   if (!iv_qkey) return fail(c, FSLR_ERR_INVALID, "fslr_cluster_path_segments: iv_qkey is NULL");
   if (n_intervals != c->ni)
     return fail(c, FSLR_ERR_INVALID, "fslr_cluster_path_segments: n_intervals " + std::to_string(n_intervals) +
                                          ", the context holds " + std::to_string(c->ni));
-  const int64_t n = c->n, ni = c->ni, n_rows = pv.n_rows, nt = pv.n_tokens;
+  // n: the real reads (on a context with virtual reads the chunks behind them are no reads of their own)
+  const bool virt = c->lg_set;
+  const int64_t n = n_real, ni = c->ni, n_rows = pv.n_rows, nt = pv.n_tokens;
+  const RealReads rr{c->rmeta, virt ? c->lg_rlen : nullptr, virt ? c->lg_off2 : nullptr};
+  if (virt && !c->lg_perm.empty() && static_cast<int64_t>(c->lg_perm.size()) != ni)
+    return fail(c, FSLR_ERR_STATE, "fslr_cluster_path_segments: the interval permutation does not span the intervals (internal)");
   if (ni > kMaxItems || n >= kMaxItems)
     return fail(c, FSLR_ERR_INVALID, "fslr_cluster_path_segments: " + std::to_string(ni) + " intervals: more than 2^30");
   if (n_rows < 0 || n_rows > n || nt < n_rows || nt > ni)
@@ -581,6 +653,15 @@ int fslr_cluster_path_segments(fslr_ctx* c, const int32_t* iv_qkey, const int32_
     if ((rc = dalloc(c, &w->rbuf, static_cast<size_t>(5 * n)))) return rc;
     w->rcap = n;
   }
+  int *lflag = nullptr, *lpos = nullptr, *longs = nullptr;
+  if (virt) {
+    if (n > w->lcap || !w->lbuf) {
+      w->lcap = 0;
+      if ((rc = dalloc(c, &w->lbuf, static_cast<size_t>(3 * (n + 1))))) return rc;
+      w->lcap = n;
+    }
+    lflag = w->lbuf, lpos = lflag + (w->lcap + 1), longs = lpos + (w->lcap + 1);
+  }
   if (n_rows > w->wcap || !w->wbuf) {
     w->wcap = 0;
     if ((rc = dalloc(c, &w->wbuf, static_cast<size_t>(2 * (n_rows + 1)))) || (rc = dalloc(c, &w->wbuf64, static_cast<size_t>(2 * (n_rows + 1)))))
@@ -603,20 +684,27 @@ int fslr_cluster_path_segments(fslr_ctx* c, const int32_t* iv_qkey, const int32_
   int *slot_k = w->tbuf, *lists = slot_k + w->tcap;           // lists: 3 x tcap
   unsigned char *slot_last = w->tbuf8, *flags = slot_last + w->tcap;   // flags: 3 x nt
   const int kbits = bits_for(n_rows + 1), ni_n = static_cast<int>(n), nw = static_cast<int>(n_rows + 1);
-  size_t tb_sort = 0, tb_s32 = 0, tb_s64 = 0, tb_sel = 0;
+  size_t tb_sort = 0, tb_s32 = 0, tb_s64 = 0, tb_sel = 0, tb_long = 0;
   HIP_TRY(c, hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, key_in, key_out, val_in, val_out, ni_n, 0, kbits, st));
   HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb_s32, nrin, rfirst, nw, st));
   HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb_s64, lk, base, nw, st));
   hipcub::CountingInputIterator<int> iota(0);
   HIP_TRY(c, hipcub::DeviceSelect::Flagged(nullptr, tb_sel, iota, flags, lists, w->cnt, static_cast<int>(std::max<int64_t>(nt, 1)), st));
-  if ((rc = ensure_temp(c, w, std::max(std::max(tb_sort, tb_sel), std::max(tb_s32, tb_s64))))) return rc;
+  if (virt) HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb_long, lflag, lpos, static_cast<int>(n + 1), st));
+  if ((rc = ensure_temp(c, w, std::max(std::max(std::max(tb_sort, tb_sel), std::max(tb_s32, tb_s64)), tb_long)))) return rc;
   int small = 0, lds = 0;
   tier_caps(&small, &lds);
   w->timed = false;
   w->ms = 0;
-  if ((rc = up(c, w, w->qkey, iv_qkey, static_cast<size_t>(ni) * sizeof(int)))) return rc;
-  if (iv_qend)
-    if ((rc = up(c, w, w->qend, iv_qend, static_cast<size_t>(ni) * sizeof(int)))) return rc;
+  if (virt && !c->lg_perm.empty()) {                // the caller's order is the real CSR's
+    if ((rc = up_perm(c, w->stage, kStageBytes, w->qkey, iv_qkey, c->lg_perm))) return rc;
+    if (iv_qend)
+      if ((rc = up_perm(c, w->stage, kStageBytes, w->qend, iv_qend, c->lg_perm))) return rc;
+  } else {
+    if ((rc = up(c, w, w->qkey, iv_qkey, static_cast<size_t>(ni) * sizeof(int)))) return rc;
+    if (iv_qend)
+      if ((rc = up(c, w, w->qend, iv_qend, static_cast<size_t>(ni) * sizeof(int)))) return rc;
+  }
   if (c->profiling) HIP_TRY(c, hipEventRecord(w->ev[0], st));     // the columns are up: the device work from here
   if (nt > 0) {
     size_t tb;
@@ -633,9 +721,19 @@ int fslr_cluster_path_segments(fslr_ctx* c, const int32_t* iv_qkey, const int32_
     k_seg_ord<<<grid_for(n), kBlock, 0, st>>>(key_out, val_out, rfirst, n, n_rows, ord);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(w->host, base + n_rows, sizeof(long long), hipMemcpyDeviceToHost, st));
+    if (virt) {
+      // the clustered reads of more than FSLR_MAX_L intervals: flag and scan; their count comes back beside n_vals
+      k_chain_long_flag<<<grid_for(n + 1), kChainBlock, 0, st>>>(pv.path_of_read, rr.rlen, n, lflag);
+      HIP_TRY(c, hipGetLastError());
+      tb = w->temp_bytes;
+      HIP_TRY(c, hipcub::DeviceScan::ExclusiveSum(w->temp, tb, lflag, lpos, static_cast<int>(n + 1), st));
+      HIP_TRY(c, hipMemcpyAsync(w->host + 1, lpos + n, sizeof(int), hipMemcpyDeviceToHost, st));
+    }
     HIP_TRY(c, hipStreamSynchronize(st));
     const int64_t n_vals = w->host[0];               // the intervals of the rows of two or more reads
-    if (n_vals < 0 || n_vals > ni) return fail(c, FSLR_ERR_STATE, "fslr_cluster_path_segments: inconsistent counts (internal)");
+    const int64_t n_long = virt ? *reinterpret_cast<const int*>(w->host + 1) : 0;
+    if (n_vals < 0 || n_vals > ni || n_long < 0 || n_long > n)
+      return fail(c, FSLR_ERR_STATE, "fslr_cluster_path_segments: inconsistent counts (internal)");
     if (n_vals > w->vcap || !w->vbuf) {
       w->vcap = 0;
       if ((rc = dalloc(c, &w->vbuf, static_cast<size_t>(3 * std::max<int64_t>(n_vals, 1))))) return rc;
@@ -646,10 +744,16 @@ int fslr_cluster_path_segments(fslr_ctx* c, const int32_t* iv_qkey, const int32_
     HIP_TRY(c, hipMemsetAsync(nr.out + 6 * nt, 0, static_cast<size_t>(3 * nt) * sizeof(int), st));
     HIP_TRY(c, hipMemsetAsync(slot_k, 0, static_cast<size_t>(nt) * sizeof(int), st));
     const long long n_quads = (n + 3) / 4;
-    EmitArgs ea{c->rmeta, c->iv, w->qkey, iv_qend ? w->qend : nullptr, pv.path_of_read, pv.flipped, ord, pv.rows, pv.tok_off, base,
+    EmitArgs ea{rr, longs, n_long, c->iv, w->qkey, iv_qend ? w->qend : nullptr, pv.path_of_read, pv.flipped, ord, pv.rows, pv.tok_off, base,
                 n, ni, n_rows, nt, n_vals, n_quads, vs, ve, vg, nr.out, slot_k, w->tbuf64, slot_last};
     k_seg_emit<<<grid_for(n_quads, kWavesPerBlock, 256 * 32), kBlock, 0, st>>>(ea);
     HIP_TRY(c, hipGetLastError());
+    if (n_long > 0) {                                // only when such reads exist, one workgroup each
+      k_chain_long_compact<<<grid_for(n), kChainBlock, 0, st>>>(lflag, lpos, n, n_long, longs);
+      HIP_TRY(c, hipGetLastError());
+      k_seg_emit_long<<<grid_for(n_long, 1, 256 * 8), kChainBlock, 0, st>>>(ea);
+      HIP_TRY(c, hipGetLastError());
+    }
     if (n_vals > 0) {
       k_seg_flags<<<grid_for(nt), kBlock, 0, st>>>(slot_k, nt, small, lds, flags);
       HIP_TRY(c, hipGetLastError());
@@ -689,6 +793,20 @@ int fslr_cluster_path_segments(fslr_ctx* c, const int32_t* iv_qkey, const int32_
   w->have = true;
   if (n_tokens_out) *n_tokens_out = nt;
   return FSLR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fslr_cluster_path_segments(fslr_ctx* c, const int32_t* iv_qkey, const int32_t* iv_qend, int64_t n_intervals,
+                               int64_t* n_tokens_out) {
+  return segments_run(c, iv_qkey, iv_qend, n_intervals, n_tokens_out, false);
+}
+
+int fslr_cluster_path_segments_any(fslr_ctx* c, const int32_t* iv_qkey, const int32_t* iv_qend, int64_t n_intervals,
+                                   int64_t* n_tokens_out) {
+  return segments_run(c, iv_qkey, iv_qend, n_intervals, n_tokens_out, true);
 }
 
 int fslr_get_cluster_path_segments(fslr_ctx* c, int32_t* start, int32_t* end, int32_t* gap, int64_t token_capacity) {

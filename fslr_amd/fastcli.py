@@ -262,6 +262,14 @@ def _run(args, basename, tsv, ints, strs, t, pool, ctx_f, state):
         write_cluster_path_segments(f'{basename}.mappings.cluster_path_segments.bed', f'{basename}.mappings.bed', trees,
                                     None if dctx is not None or args.get('cluster_loci') or args.get('cluster_junctions') or
                                     args.get('cluster_paths') else g, cmap)
+    if args.get('cluster_path_segments_any'):
+        from .main import write_cluster_path_segments
+        # an earlier flag made the graph's table, unless it only printed its notice about long reads
+        chains = (args.get('cluster_junctions') or args.get('cluster_paths')) and \
+            (args.get('cluster_long_reads') or getattr(trees, 'long', None) is None)
+        write_cluster_path_segments(f'{basename}.mappings.cluster_path_segments.bed', f'{basename}.mappings.bed', trees,
+                                    None if dctx is not None or args.get('cluster_loci') or chains else g, cmap,
+                                    any_length=True)
     t['write'] = time.perf_counter() - t3
     # the device buffers go now (the caller's process would free them at exit anyway)
     t5 = time.perf_counter()

@@ -122,7 +122,12 @@ def assign_clusters(bed_file: pd.DataFrame, G: cluster.ClusterGraph, ctx=None):
               help='Also write {name}.mappings.cluster_path_segments.bed: per piece of every cluster path its consensus '
                    '(median) coordinates with their extrema over the reads that walk the path, and the query-space gap '
                    'to the next piece (negative: overlap, positive: inserted sequence); loads as BED (one GPU; an '
-                   'input with reads of more than 64 intervals prints a notice and writes no file)')
+                   'input with reads of more than 64 intervals prints a notice and writes no file: '
+                   '--cluster-path-segments-any takes it)')
+@click.option('--cluster-path-segments-any', required=False, is_flag=True,
+              help='Write {name}.mappings.cluster_path_segments.bed as --cluster-path-segments does, for any input: reads '
+                   'of more than 64 intervals (up to 4096) are taken too (fslr_cluster_paths_any / '
+                   'fslr_cluster_path_segments_any); without such reads the file is the same, byte for byte (one GPU)')
 @click.option('--cluster-long-reads', required=False, is_flag=True,
               help='With --cluster-junctions / --cluster-paths: also take inputs that hold reads of more than 64 '
                    'intervals (up to 4096; fslr_cluster_junctions_any / fslr_cluster_paths_any) instead of printing a '
@@ -152,6 +157,8 @@ def pipeline(**args):
         raise click.UsageError('--cluster-paths needs the whole index on one device: run it with --gpus 1')
     if args.get('cluster_path_segments') and (args.get('gpus') or 1) > 1:
         raise click.UsageError('--cluster-path-segments needs the whole index on one device: run it with --gpus 1')
+    if args.get('cluster_path_segments_any') and (args.get('gpus') or 1) > 1:
+        raise click.UsageError('--cluster-path-segments-any needs the whole index on one device: run it with --gpus 1')
     if not os.path.exists(args['out']):
         os.mkdir(args['out'])
     if not args['skip_alignment']:
@@ -318,17 +325,19 @@ SEGMENT_COLUMNS = ('chrom', 'start', 'end', 'cluster', 'path', 'piece', 'strand'
                    'end_min', 'end_max', 'gap_min', 'gap', 'gap_max')
 
 
-def write_cluster_path_segments(path, bed_path, trees, G_or_labels, chrom_to_num_map):
+def write_cluster_path_segments(path, bed_path, trees, G_or_labels, chrom_to_num_map, any_length=False):
     """--cluster-path-segments: one line per piece of every cluster path (cluster.ClusterPathSegments.to_frame) as a
     tab-separated file with SEGMENT_COLUMNS: chrom, median start and median end first, so it loads as BED;
     chromosome names as in the input.  An index with reads of more than 64 intervals prints a notice and writes
-    nothing (--cluster-long-reads does not lift this)."""
-    if getattr(trees, 'long', None) is not None:
+    nothing (--cluster-long-reads does not lift this), unless ``any_length`` (--cluster-path-segments-any) sends the
+    call through cluster_path_segments_any."""
+    if getattr(trees, 'long', None) is not None and not any_length:
         print('--cluster-path-segments: the input holds reads of more than 64 intervals; no path segments file is '
-              'written.')
+              'written (--cluster-path-segments-any takes such an input).')
         return False
     qstart, rev, qend = junction_inputs(bed_path, trees.data.index, with_qend=True)
-    frame = trees.cluster_path_segments(qstart, qend, rev, G_or_labels).to_frame()
+    call = trees.cluster_path_segments_any if any_length else trees.cluster_path_segments
+    frame = call(qstart, qend, rev, G_or_labels).to_frame()
     name_of = {v: k for k, v in chrom_to_num_map.items()}
     frame['chrom'] = [name_of.get(c, c) for c in frame['chrom'].tolist()]      # (--cluster-paths named its rows' loci)
     frame[list(SEGMENT_COLUMNS)].to_csv(path, sep='\t', index=False)
@@ -406,6 +415,13 @@ def _cluster_and_write(args, basename, bed_file, tsv, t):
                                     interval_tree,
                                     None if args.get('cluster_loci') or args.get('cluster_junctions') or
                                     args.get('cluster_paths') else network, chrom_to_num_map)
+    if args.get('cluster_path_segments_any'):
+        # an earlier flag made the graph's table, unless it only printed its notice about long reads
+        chains = (args.get('cluster_junctions') or args.get('cluster_paths')) and \
+            (args.get('cluster_long_reads') or getattr(interval_tree, 'long', None) is None)
+        write_cluster_path_segments(f'{basename}.mappings.cluster_path_segments.bed', f'{basename}.mappings.bed',
+                                    interval_tree, None if args.get('cluster_loci') or chains else network,
+                                    chrom_to_num_map, any_length=True)
     t['write'] = time.perf_counter() - t3
     if args.get('timings'):
         st = network.stats

@@ -881,6 +881,28 @@ int  fslr_get_cluster_path_segments(fslr_ctx *ctx, int32_t *start /* [3 x n_toke
                                     int64_t token_capacity);
 int  fslr_cluster_path_segments_timings(fslr_ctx *ctx, float *ms);
 
+/* Path segments for reads of any length: fslr_cluster_path_segments for a context that holds virtual reads
+ * (fslr_set_reads_any, fslr_set_long_reads), as fslr_cluster_paths_any stands beside fslr_cluster_paths.  The
+ * contract is the one above, read for real reads of 1..FSLR_MAX_ANY_L intervals.
+ *   Inputs      iv_qkey / iv_qend (may be NULL: the gap columns are all 0) in the REAL CSR's interval order,
+ *               n_intervals the real interval count: the order fslr_cluster_paths_any takes its columns in (the call
+ *               brings them to the virtual order itself; after fslr_set_long_reads the two orders are the same).
+ *   Chain       all the intervals of real read r, the chunks behind its first FSLR_MAX_L included, ordered by
+ *               (iv_qkey ascending, position in the real list ascending on equal keys).  A chunk is never a read
+ *               of its own; the link between positions FSLR_MAX_L - 1 and FSLR_MAX_L is a link like any other.
+ *   Path rows   the resident ones of the current table, made by fslr_cluster_paths_any; path_of_read and flipped
+ *               are per real read.
+ *   Rows        the resident rows of the plain call: fslr_get_cluster_path_segments and
+ *               fslr_cluster_path_segments_timings answer for them, whatever drops or frees those rows drops or
+ *               frees these, a failed call keeps the previous rows.
+ *   Errors      those of the plain call without the refusal of virtual reads.  FSLR_ERR_INVALID beyond 2^30
+ *               intervals.
+ *   On a context without virtual reads the call runs the code of the plain call and leaves the same bytes.
+ *   A clustered read of more than FSLR_MAX_L intervals takes one workgroup (its chain is sorted in LDS); the
+ *   selection tiers, FSLR_SEGS_SMALL and FSLR_SEGS_LDS keep their meaning: k counts the reads of a row, whatever
+ *   their length.  One GPU: the whole index on the context. */
+int  fslr_cluster_path_segments_any(fslr_ctx *ctx, const int32_t *iv_qkey, const int32_t *iv_qend, int64_t n_intervals, int64_t *n_tokens);
+
 /* Match reads that are NOT in the uploaded set against the resident index: for a query read Q, given
  * like a row of fslr_reads (its intervals in the order its loop walks them, dense chromosome ids of the
  * uploaded CSR, folded iv_thr, its qlen2 and n_alignments), what the reference's pair loop
