@@ -57,7 +57,8 @@ EXPORTED = ['fslr_abi_version', 'fslr_last_error', 'fslr_ctx_create', 'fslr_ctx_
             'fslr_cluster_paths', 'fslr_get_cluster_paths', 'fslr_cluster_paths_timings',
             'fslr_cluster_junctions_any', 'fslr_cluster_paths_any',
             'fslr_cluster_path_segments', 'fslr_get_cluster_path_segments', 'fslr_cluster_path_segments_timings',
-            'fslr_cluster_path_segments_any']
+            'fslr_cluster_path_segments_any',
+            'fslr_cluster_path_containment', 'fslr_get_cluster_path_containment', 'fslr_cluster_path_containment_timings']
 # fslr_score_pairs' flag bits (include/fslr_hip.h)
 SCORE_GATE, SCORE_EDGE, SCORE_ZD_GATE, SCORE_ZD_OVERLAP = 1, 2, 4, 8
 # fslr_coverage_*: keys per tile of the sorted arrays, queries per chunk (include/fslr_hip.h)
@@ -290,6 +291,9 @@ def load(path: str = LIB_PATH):
         'fslr_cluster_path_segments_any': (ctypes.c_int, [vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int64)]),
         'fslr_get_cluster_path_segments': (ctypes.c_int, [vp, vp, vp, vp, i64]),
         'fslr_cluster_path_segments_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        'fslr_cluster_path_containment': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64)]),
+        'fslr_get_cluster_path_containment': (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64]),
+        'fslr_cluster_path_containment_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1455,6 +1459,7 @@ class Context:
                          None if rev is None else _ptr(rev) if rev.size else _ptr(np.zeros(1, np.uint8)),
                          int(qkey.size), ctypes.byref(nr), ctypes.byref(nt)))
         nr, nt, n = int(nr.value), int(nt.value), self._n_real_reads()
+        self._n_path_rows = nr                     # cluster_path_containment sizes its per-row outputs by it
         ci = getattr(self, '_cluster_info', None) or {'n_clusters': 0}
         off, tok_off = np.zeros(ci['n_clusters'] + 1, np.int64), np.zeros(nr + 1, np.int64)
         n_reads, first_read, locus, path = (np.empty(k, np.int32) for k in (nr, nr, nt, n))
@@ -1507,3 +1512,35 @@ class Context:
         ms = (ctypes.c_float * 1)()
         self._check(self._L.fslr_cluster_path_segments_timings(self._h, ms))
         return {'segments': float(ms[0])}
+
+    # -- path containment (fslr_hip.h fslr_cluster_path_containment) ------------------------------------
+    def cluster_path_containment(self):
+        """Which of the resident path rows (cluster_paths / cluster_paths_any first) are contiguous sub-chains of a
+        longer row of their cluster, in either reading direction, and each row's support with them counted.
+        Nothing is uploaded.  Returns ``(coff int64[n_rows + 1], outer int32, offset int32, rev uint8, n_occ int32,
+        n_inner int32, support int64, collapse_to int32, collapsed_reads int64)``: the pairs of inner row A are
+        ``coff[A]:coff[A + 1]`` of the four pair columns, the last four columns are per path row."""
+        n = ctypes.c_int64(0)
+        self._check(self._L.fslr_cluster_path_containment(self._h, ctypes.byref(n)))
+        # the per-row outputs are sized by the rows this context's last cluster_paths* made; the library refuses a
+        # smaller capacity than its own row count, and a larger one is cut back below
+        npairs, n_rows = int(n.value), int(getattr(self, '_n_path_rows', 0))
+        coff = np.full(n_rows + 1, -1, np.int64)
+        outer, offset, n_occ = (np.empty(npairs, np.int32) for _ in range(3))
+        rev = np.empty(npairs, np.uint8)
+        n_inner, collapse_to = np.empty(n_rows, np.int32), np.empty(n_rows, np.int32)
+        support, collapsed = np.empty(n_rows, np.int64), np.empty(n_rows, np.int64)
+        self._check(self._L.fslr_get_cluster_path_containment(
+            self._h, _ptr(coff), _ptr(outer), _ptr(offset), _ptr(rev), _ptr(n_occ), _ptr(n_inner), _ptr(support),
+            _ptr(collapse_to), _ptr(collapsed), n_rows, npairs))
+        have = int((coff >= 0).sum()) - 1                # the library wrote coff[0 .. its rows]: offsets, never negative
+        if have != n_rows:                               # (path rows made past this wrapper): keep what was written
+            coff, n_inner, support = coff[:have + 1], n_inner[:have], support[:have]
+            collapse_to, collapsed = collapse_to[:have], collapsed[:have]
+        return (coff, outer, offset, rev, n_occ, n_inner, support, collapse_to, collapsed)
+
+    def cluster_path_containment_timings(self) -> dict:
+        """HIP-event time (ms) of the last cluster_path_containment (profiling contexts)."""
+        ms = (ctypes.c_float * 1)()
+        self._check(self._L.fslr_cluster_path_containment_timings(self._h, ms))
+        return {'containment': float(ms[0])}

@@ -52,7 +52,7 @@ __all__ = ['IntervalItem', 'keep_fillings', 'rename_chromosomes', 'chrom_to_str'
            'calculate_overlap', 'overall_jaccard_similarity', 'different_lengths_or_alignments', 'PairScores',
            'PairMatching',
            'device_coverage', 'DeviceCoverage', 'ClusterTable', 'cluster_table', 'ClusterLoci',
-           'ClusterJunctions', 'ClusterPaths', 'ClusterPathSegments']
+           'ClusterJunctions', 'ClusterPaths', 'ClusterPathSegments', 'ClusterPathContainment']
 
 
 class EdgeCapWarning(UserWarning):
@@ -705,6 +705,52 @@ class ClusterPathSegments:
                         zip(ch, self.start_med[a:b].tolist(), self.end_med[a:b].tolist(), p.rev[a:b].tolist()))
 
 
+class ClusterPathContainment:
+    """DeviceIntervalIndex.cluster_path_containment's result (fslr_cluster_path_containment): which rows of ``paths``
+    (the ClusterPaths it was made on) are contiguous sub-chains of a longer row of their cluster, in either reading
+    direction, and each row's support with those counted.  The pairs of inner row A are ``coff[A]:coff[A + 1]`` of
+    ``outer`` (the containing row), ``offset`` (the smallest offset of A in it), ``rev`` (1: A lies there reverse
+    complemented) and ``n_occ`` (its occurrences); pairs ascend by (inner, outer).  Per path row: ``n_inner`` rows
+    it contains, ``support`` = its reads plus theirs, ``collapse_to`` = itself when nothing contains it (it is
+    maximal), else the maximal row with the largest support among those that contain it (ties to the smaller row),
+    ``collapsed_reads`` = the reads of a maximal row and of the rows that collapse to it, 0 for the others."""
+
+    PAIR_NAMES = ('outer', 'offset', 'rev', 'n_occ')
+    ROW_NAMES = ('n_inner', 'support', 'collapse_to', 'collapsed_reads')
+
+    def __init__(self, paths, coff, outer, offset, rev, n_occ, n_inner, support, collapse_to, collapsed_reads):
+        self.paths, self.coff = paths, coff
+        self.outer, self.offset, self.rev, self.n_occ = outer, offset, rev, n_occ
+        self.n_inner, self.support, self.collapse_to, self.collapsed_reads = n_inner, support, collapse_to, collapsed_reads
+
+    def __len__(self):
+        return int(self.outer.shape[0])
+
+    def inner_of_pair(self) -> np.ndarray:
+        """The inner row of every pair."""
+        return np.repeat(np.arange(self.coff.shape[0] - 1, dtype=np.int64), np.diff(self.coff))
+
+    def maximal(self) -> np.ndarray:
+        """Per path row: nothing contains it."""
+        return np.diff(self.coff) == 0
+
+    def to_frame(self):
+        """One line per containment pair: ``cluster, inner, outer`` (global path rows), ``offset, rev, n_occ``."""
+        inner = self.inner_of_pair()
+        cl = self.paths.cluster_of_row()[inner] if len(self) else np.zeros(0, np.int64)
+        return pd.DataFrame({'cluster': cl, 'inner': inner, 'outer': self.outer, 'offset': self.offset,
+                             'rev': self.rev, 'n_occ': self.n_occ})
+
+    def paths_frame(self):
+        """One line per path row: ``cluster, row`` (the global path row), ``n_tokens, n_reads, n_inner, support,
+        maximal, collapse_to, collapsed_reads``."""
+        p = self.paths
+        return pd.DataFrame({'cluster': p.cluster_of_row(), 'row': np.arange(len(p), dtype=np.int64),
+                             'n_tokens': np.diff(p.tok_off), 'n_reads': p.n_reads, 'n_inner': self.n_inner,
+                             'support': self.support, 'maximal': self.maximal(), 'collapse_to': self.collapse_to,
+                             'collapsed_reads': self.collapsed_reads})
+
+
 def _rev_bits(strand) -> np.ndarray:
     """uint8 0/1 of a strand column given as booleans, 0/1 or '+' / '-' ('-' and true values are 1)."""
     s = np.asarray(strand)
@@ -1281,21 +1327,49 @@ class DeviceIntervalIndex:
             if e.dtype.kind not in 'iu' or (e.size and (e.min() < -(1 << 31) or e.max() >= (1 << 31))):
                 raise ValueError('qend must hold int32 values')
             qe = e[np.asarray(self.csr.data_pos, np.int64)].astype(np.int32)
-        made = self.__dict__.get('_paths_made')
-        if G_or_labels is None and made is not None and made[0] is not None and \
-                made[0] is getattr(self.ctx, '_cluster_info', None):
-            q = np.asarray(qstart)
-            rev = None if strand is None else _rev_bits(strand)
-            pos = np.asarray(self.csr.data_pos, np.int64)
-            if q.shape == (n,) and q.dtype.kind in 'iu' and np.array_equal(q[pos], made[1]) and \
-                    (rev is None) == (made[2] is None) and (rev is None or (rev.shape == (n,) and np.array_equal(rev[pos], made[2]))):
-                try:
-                    return ClusterPathSegments(made[3], *segments(made[1], qe))
-                except FslrError as err:                 # the rows were dropped since (cluster_loci again): make them
-                    if 'no cluster paths' not in str(err):
-                        raise
+        made = self._paths_to_reuse(qstart, strand, G_or_labels)
+        if made is not None:
+            try:
+                return ClusterPathSegments(made[3], *segments(made[1], qe))
+            except FslrError as err:                     # the rows were dropped since (cluster_loci again): make them
+                if 'no cluster paths' not in str(err):
+                    raise
         paths = make_paths(qstart, strand, G_or_labels)
         return ClusterPathSegments(paths, *segments(self._paths_made[1], qe))
+
+    def _paths_to_reuse(self, qstart, strand, G_or_labels):
+        """What cluster_paths* remembered (table, qkey, rev, ClusterPaths) when a call on the resident path rows may
+        reuse it: no new table is asked for, the context's table is still the one the rows were made on, and
+        ``qstart`` and ``strand`` are the columns they were made with.  None otherwise."""
+        made = self.__dict__.get('_paths_made')
+        if G_or_labels is not None or made is None or made[0] is None or \
+                made[0] is not getattr(self.ctx, '_cluster_info', None):
+            return None
+        n = int(self.csr.n_intervals)
+        q = np.asarray(qstart)
+        rev = None if strand is None else _rev_bits(strand)
+        pos = np.asarray(self.csr.data_pos, np.int64)
+        if q.shape == (n,) and q.dtype.kind in 'iu' and np.array_equal(q[pos], made[1]) and \
+                (rev is None) == (made[2] is None) and (rev is None or (rev.shape == (n,) and np.array_equal(rev[pos], made[2]))):
+            return made
+        return None
+
+    def cluster_path_containment(self, qstart, strand=None, G_or_labels=None) -> ClusterPathContainment:
+        """Which cluster paths are only truncated views of another path, and a full-length path's support once the
+        truncated reads are counted (fslr_cluster_path_containment).  ``qstart``, ``strand`` and ``G_or_labels`` are
+        cluster_paths_any's; the table's loci and paths are made when needed and the path rows this index made with
+        the same ``qstart`` and ``strand`` since its last table are reused (the rule of cluster_path_segments_any).
+        The call works on the path rows alone, so an index with reads of more than 64 intervals is taken as any
+        other.  The result holds its ClusterPaths as ``.paths``."""
+        made = self._paths_to_reuse(qstart, strand, G_or_labels)
+        if made is not None:
+            try:
+                return ClusterPathContainment(made[3], *self.ctx.cluster_path_containment())
+            except FslrError as err:                     # the rows were dropped since (cluster_loci again): make them
+                if 'no cluster paths' not in str(err):
+                    raise
+        paths = self.cluster_paths_any(qstart, strand, G_or_labels)
+        return ClusterPathContainment(paths, *self.ctx.cluster_path_containment())
 
     def __getitem__(self, chrom):
         return ChromosomeView(self, chrom)
@@ -1453,6 +1527,11 @@ class MultiGpuIndex:
         raise NotImplementedError('a multi-GPU index lives in the rank processes and cannot give path segments from '
                                   'here (fslr_cluster_path_segments needs the whole index on one context); build it '
                                   'with n_gpus=1')
+
+    def cluster_path_containment(self, *args, **kwargs):
+        raise NotImplementedError('a multi-GPU index lives in the rank processes and cannot give path containment '
+                                  'from here (fslr_cluster_path_containment needs the path rows on one context); '
+                                  'build it with n_gpus=1')
 
     def cluster_junctions_any(self, *args, **kwargs):
         return self.cluster_junctions(*args, **kwargs)

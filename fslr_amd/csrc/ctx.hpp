@@ -190,6 +190,7 @@ struct fslr_ctx {
   struct JunctionWork* jnw = nullptr;    // fslr_cluster_junctions' resident rows, its scratch and its last call's time (junctions.hip)
   struct PathWork* ptw = nullptr;        // fslr_cluster_paths' resident rows, its scratch and its last call's time (paths.hip)
   struct SegmentWork* sgw = nullptr;     // fslr_cluster_path_segments' resident rows, its scratch and its last call's time (segments.hip)
+  struct ContainmentWork* ctw = nullptr; // fslr_cluster_path_containment's resident rows, its scratch and its last call's time (containment.hip)
   // reads of more than FSLR_MAX_L intervals (long.hip): the virtual-read map and the long-pair stage
   bool lg_set = false;
   // fslr_set_reads_any: virtual interval k is real interval lg_perm[k] (thresholds arrive in the real
@@ -263,19 +264,26 @@ void fslr_junctions_drop(fslr_ctx* c);
 // their tokens name are dropped or replaced)
 void fslr_paths_free(fslr_ctx* c);
 void fslr_paths_drop(fslr_ctx* c);
-// the resident path rows for fslr_cluster_path_segments (paths.hip): false without rows; rows = [2 x n_rows]
-// n_reads, first_read; n = the reads path_of_read and flipped hold
+// the resident path rows for fslr_cluster_path_segments and fslr_cluster_path_containment (paths.hip): false
+// without rows; rows = [2 x n_rows] n_reads, first_read; n = the reads path_of_read and flipped hold; locus / rev
+// = the tokens [n_tokens]
 struct fslr_paths_rows {
   const long long* tok_off;
   const int *rows, *path_of_read;
   const unsigned char* flipped;
   int64_t n_rows, n_tokens, n_clusters, n;
+  const int* locus;
+  const unsigned char* rev;
 };
 bool fslr_paths_view(const fslr_ctx* c, fslr_paths_rows* v);
 // frees the path segments' rows and scratch (segments.hip); fslr_segments_drop forgets the rows alone (the path
 // rows whose slots they fill are dropped or replaced)
 void fslr_segments_free(fslr_ctx* c);
 void fslr_segments_drop(fslr_ctx* c);
+// frees the path containment's rows and scratch (containment.hip); fslr_containment_drop forgets the rows alone
+// (the path rows they name are dropped or replaced)
+void fslr_containment_free(fslr_ctx* c);
+void fslr_containment_drop(fslr_ctx* c);
 // frees the read matching's buffers and its saved batch (match.hip)
 void fslr_match_free(fslr_ctx* c);
 // frees the append's batch scratch and its second set of data-order buffers (append.hip)

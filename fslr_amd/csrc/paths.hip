@@ -100,12 +100,14 @@ void dfree(T*& p) {
 void fslr_paths_drop(fslr_ctx* c) {
   if (c->ptw) c->ptw->have = false;
   fslr_segments_drop(c);                    // the segments fill these rows' slots
+  fslr_containment_drop(c);                 // the containment rows name these rows
 }
 
 bool fslr_paths_view(const fslr_ctx* c, fslr_paths_rows* v) {
   const PathWork* w = c->ptw;
   if (!w || !w->have) return false;
-  *v = fslr_paths_rows{w->tok_off, w->rows, w->path_of_read, w->flipped, w->n_rows, w->n_tokens, w->n_clusters, w->n};
+  *v = fslr_paths_rows{w->tok_off, w->rows, w->path_of_read, w->flipped, w->n_rows, w->n_tokens, w->n_clusters, w->n,
+                       w->locus, w->rev};
   return true;
 }
 
@@ -775,6 +777,7 @@ int paths_run(fslr_ctx* c, const int32_t* iv_qkey, const uint8_t* iv_rev, int64_
   }
   // install
   fslr_segments_drop(c);                    // segments of the rows that go
+  fslr_containment_drop(c);                 // and the containment rows that name them
   std::swap(w->off, nr.off);
   std::swap(w->tok_off, nr.tok_off);
   std::swap(w->rows, nr.rows);

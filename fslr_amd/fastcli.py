@@ -270,6 +270,11 @@ def _run(args, basename, tsv, ints, strs, t, pool, ctx_f, state):
         write_cluster_path_segments(f'{basename}.mappings.cluster_path_segments.bed', f'{basename}.mappings.bed', trees,
                                     None if dctx is not None or args.get('cluster_loci') or chains else g, cmap,
                                     any_length=True)
+    if args.get('cluster_path_containment'):
+        from .main import write_cluster_path_containment
+        # the graph's table is made anew: whatever an earlier flag left (or, for long reads, did not make) is replaced
+        write_cluster_path_containment(f'{basename}.mappings.cluster_path_containment.bed', f'{basename}.mappings.bed',
+                                       trees, g)
     t['write'] = time.perf_counter() - t3
     # the device buffers go now (the caller's process would free them at exit anyway)
     t5 = time.perf_counter()

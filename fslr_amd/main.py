@@ -128,6 +128,11 @@ def assign_clusters(bed_file: pd.DataFrame, G: cluster.ClusterGraph, ctx=None):
               help='Write {name}.mappings.cluster_path_segments.bed as --cluster-path-segments does, for any input: reads '
                    'of more than 64 intervals (up to 4096) are taken too (fslr_cluster_paths_any / '
                    'fslr_cluster_path_segments_any); without such reads the file is the same, byte for byte (one GPU)')
+@click.option('--cluster-path-containment', required=False, is_flag=True,
+              help='Also write {name}.mappings.cluster_path_containment.bed: per cluster path the paths it contains as '
+                   'truncated views (contiguous sub-chains in either direction), its support with their reads counted, '
+                   'the full-length path it collapses to, and the paths that contain it as outer:offset:strand (one '
+                   'GPU; any input, reads of more than 64 intervals included)')
 @click.option('--cluster-long-reads', required=False, is_flag=True,
               help='With --cluster-junctions / --cluster-paths: also take inputs that hold reads of more than 64 '
                    'intervals (up to 4096; fslr_cluster_junctions_any / fslr_cluster_paths_any) instead of printing a '
@@ -159,6 +164,8 @@ def pipeline(**args):
         raise click.UsageError('--cluster-path-segments needs the whole index on one device: run it with --gpus 1')
     if args.get('cluster_path_segments_any') and (args.get('gpus') or 1) > 1:
         raise click.UsageError('--cluster-path-segments-any needs the whole index on one device: run it with --gpus 1')
+    if args.get('cluster_path_containment') and (args.get('gpus') or 1) > 1:
+        raise click.UsageError('--cluster-path-containment needs the whole index on one device: run it with --gpus 1')
     if not os.path.exists(args['out']):
         os.mkdir(args['out'])
     if not args['skip_alignment']:
@@ -344,6 +351,27 @@ def write_cluster_path_segments(path, bed_path, trees, G_or_labels, chrom_to_num
     return True
 
 
+CONTAINMENT_COLUMNS = ('cluster', 'row', 'n_tokens', 'n_reads', 'n_inner', 'support', 'maximal', 'collapse_to',
+                       'collapsed_reads', 'contained_in')
+
+
+def write_cluster_path_containment(path, bed_path, trees, G_or_labels):
+    """--cluster-path-containment: one line per path row of ``trees``' clusters
+    (cluster.ClusterPathContainment.paths_frame) as a tab-separated file with CONTAINMENT_COLUMNS; ``maximal`` is 0 / 1
+    and ``contained_in`` lists the rows that contain this one as ``outer:offset:strand`` joined by ``,`` (``-``: it
+    lies there reverse complemented; ``.`` for a row nothing contains).  Any input is taken: the call goes through
+    cluster_paths_any."""
+    qstart, rev = junction_inputs(bed_path, trees.data.index)
+    res = trees.cluster_path_containment(qstart, rev, G_or_labels)
+    frame = res.paths_frame()
+    frame['maximal'] = frame['maximal'].astype(np.int64)
+    entry = [f'{o}:{f}:' + '-+'[r == 0] for o, f, r in zip(res.outer.tolist(), res.offset.tolist(), res.rev.tolist())]
+    co = res.coff.tolist()
+    frame['contained_in'] = np.asarray([','.join(entry[a:b]) or '.' for a, b in zip(co[:-1], co[1:])], dtype=object)
+    frame[list(CONTAINMENT_COLUMNS)].to_csv(path, sep='\t', index=False)
+    return True
+
+
 def _cluster_and_write(args, basename, bed_file, tsv, t):
     chromosome_mask = set()
     if args['cluster_mask']:
@@ -422,6 +450,10 @@ def _cluster_and_write(args, basename, bed_file, tsv, t):
         write_cluster_path_segments(f'{basename}.mappings.cluster_path_segments.bed', f'{basename}.mappings.bed',
                                     interval_tree, None if args.get('cluster_loci') or chains else network,
                                     chrom_to_num_map, any_length=True)
+    if args.get('cluster_path_containment'):
+        # the graph's table is made anew: whatever an earlier flag left (or, for long reads, did not make) is replaced
+        write_cluster_path_containment(f'{basename}.mappings.cluster_path_containment.bed', f'{basename}.mappings.bed',
+                                       interval_tree, network)
     t['write'] = time.perf_counter() - t3
     if args.get('timings'):
         st = network.stats

@@ -903,6 +903,55 @@ int  fslr_cluster_path_segments_timings(fslr_ctx *ctx, float *ms);
  *   their length.  One GPU: the whole index on the context. */
 int  fslr_cluster_path_segments_any(fslr_ctx *ctx, const int32_t *iv_qkey, const int32_t *iv_qend, int64_t n_intervals, int64_t *n_tokens);
 
+/* Path containment: which path rows are only truncated views of another row of their cluster, and what a
+ * full-length row's support is once the truncated reads are counted.  A read that lost a piece at either end has
+ * a path of its own in fslr_cluster_paths; this call finds, per cluster, the rows that are contiguous sub-chains of
+ * a longer row, in either reading direction.  On top of the resident path rows of the current table alone
+ * (fslr_cluster_paths / fslr_cluster_paths_any): no CSR, no uploaded column, no virtual reads, so one call serves
+ * contexts with and without reads of more than FSLR_MAX_L intervals (a path row of up to FSLR_MAX_ANY_L tokens is
+ * an ordinary row).
+ *   Terms: row A has the tokens A[0..a-1], t = locus * 2 + rev; rc(A)[i] = A[a-1-i] ^ 1; A is palindromic when
+ *   rc(A) == A.
+ *   Containment: row A is contained in row B iff they lie in the same cluster, a < b, and there is an offset o in
+ *   [0, b - a] and a direction d with B[o + i] == A[i] for all i (d = 0) or B[o + i] == rc(A)[i] for all i
+ *   (d = 1).  Each such (o, d) is an occurrence.  For a palindromic A only d = 0 is probed, so the occurrences of
+ *   a pair always have distinct offsets.  Rows of equal length are never contained in one another (two distinct
+ *   canonical rows can be neither equal nor reverse complements) and are not probed.  Tokens of different
+ *   clusters never compare equal, because a token names a loci row and the loci rows are per cluster: the
+ *   same-cluster condition needs no check of its own.  Containment is transitive.
+ *   Containment rows: one per contained pair (A, B), ordered by (A ascending, B ascending), behind
+ *   coff[n_rows + 1] (indexed by the inner row A).  Columns: outer (B's global row), offset (the smallest offset
+ *   among the pair's occurrences), rev (the direction of the occurrence at that offset), n_occ (the pair's
+ *   occurrences).
+ *   Per path row: n_inner (how many rows it contains); support (its n_reads plus the n_reads of every row it
+ *   contains); collapse_to (the row itself when nothing contains it: it is maximal; otherwise, among the rows
+ *   that contain it and are themselves maximal, the one with the largest support, ties to the smallest row:
+ *   containment is transitive, so one always exists); collapsed_reads (for a maximal row its n_reads plus the
+ *   n_reads of the rows that collapse to it, 0 for the others: the collapsed_reads of a cluster's rows sum to the
+ *   cluster's size).  No path rows give empty outputs (coff = {0}).  The bytes are the same on every run.
+ * fslr_cluster_path_containment: computes the rows and keeps them resident (*n_pairs, may be NULL); syncs.
+ *   FSLR_ERR_STATE, named in the message: no cluster table; no resident path rows of this table
+ *   (fslr_cluster_paths first).  FSLR_ERR_INVALID when the occurrences exceed 2^30 (the message names the
+ *   count).  A failed call keeps the previous rows, a successful one replaces them; whatever drops or replaces
+ *   the path rows (fslr_cluster_table, a successful fslr_cluster_loci, a successful fslr_cluster_paths /
+ *   fslr_cluster_paths_any) drops them; fslr_ctx_destroy frees them.  The path, segment, junction and loci rows
+ *   and all query state are left alone.  A table that went stale after fslr_append_reads* / fslr_remove_reads*
+ *   still describes its path rows: the call reads no read and keeps answering for them.
+ *   An inner row of at most 64 tokens is probed by a lane group, a longer one by a workgroup; every candidate
+ *   comes from an index of the token occurrences, anchored at the inner row's first token (forward) and at its
+ *   last token ^ 1 (reverse).
+ * fslr_get_cluster_path_containment: D2H of the rows (NULL outputs are skipped): coff[n_rows + 1]; outer, offset,
+ *   rev, n_occ [n_pairs]; n_inner, support, collapse_to, collapsed_reads [n_rows].  FSLR_ERR_STATE without rows,
+ *   FSLR_ERR_INVALID when row_capacity < n_rows or pair_capacity < n_pairs (nothing is written).
+ * fslr_cluster_path_containment_timings (fslr_set_profiling 1 or 2): HIP-event time (ms[0]) of the last
+ *   fslr_cluster_path_containment, from its first operation on the stream to its last; FSLR_ERR_STATE when it
+ *   was not profiled. */
+int  fslr_cluster_path_containment(fslr_ctx *ctx, int64_t *n_pairs);
+int  fslr_get_cluster_path_containment(fslr_ctx *ctx, int64_t *coff, int32_t *outer, int32_t *offset, uint8_t *rev, int32_t *n_occ,
+                                       int32_t *n_inner, int64_t *support, int32_t *collapse_to, int64_t *collapsed_reads,
+                                       int64_t row_capacity, int64_t pair_capacity);
+int  fslr_cluster_path_containment_timings(fslr_ctx *ctx, float *ms);
+
 /* Match reads that are NOT in the uploaded set against the resident index: for a query read Q, given
  * like a row of fslr_reads (its intervals in the order its loop walks them, dense chromosome ids of the
  * uploaded CSR, folded iv_thr, its qlen2 and n_alignments), what the reference's pair loop
