@@ -58,7 +58,9 @@ EXPORTED = ['fslr_abi_version', 'fslr_last_error', 'fslr_ctx_create', 'fslr_ctx_
             'fslr_cluster_junctions_any', 'fslr_cluster_paths_any',
             'fslr_cluster_path_segments', 'fslr_get_cluster_path_segments', 'fslr_cluster_path_segments_timings',
             'fslr_cluster_path_segments_any',
-            'fslr_cluster_path_containment', 'fslr_get_cluster_path_containment', 'fslr_cluster_path_containment_timings']
+            'fslr_cluster_path_containment', 'fslr_get_cluster_path_containment', 'fslr_cluster_path_containment_timings',
+            'fslr_cluster_collapsed_segments', 'fslr_cluster_collapsed_segments_any',
+            'fslr_get_cluster_collapsed_segments', 'fslr_cluster_collapsed_segments_timings']
 # fslr_score_pairs' flag bits (include/fslr_hip.h)
 SCORE_GATE, SCORE_EDGE, SCORE_ZD_GATE, SCORE_ZD_OVERLAP = 1, 2, 4, 8
 # fslr_coverage_*: keys per tile of the sorted arrays, queries per chunk (include/fslr_hip.h)
@@ -294,6 +296,10 @@ def load(path: str = LIB_PATH):
         'fslr_cluster_path_containment': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int64)]),
         'fslr_get_cluster_path_containment': (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64]),
         'fslr_cluster_path_containment_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
+        'fslr_cluster_collapsed_segments': (ctypes.c_int, [vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int64)]),
+        'fslr_cluster_collapsed_segments_any': (ctypes.c_int, [vp, vp, vp, i64, ctypes.POINTER(ctypes.c_int64)]),
+        'fslr_get_cluster_collapsed_segments': (ctypes.c_int, [vp, vp, vp, vp, vp, vp, i64]),
+        'fslr_cluster_collapsed_segments_timings': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_float)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1544,3 +1550,46 @@ class Context:
         ms = (ctypes.c_float * 1)()
         self._check(self._L.fslr_cluster_path_containment_timings(self._h, ms))
         return {'containment': float(ms[0])}
+
+    # -- collapsed path segments (fslr_hip.h fslr_cluster_collapsed_segments) ---------------------------
+    def cluster_collapsed_segments(self, qkey, qend=None):
+        """Consensus coordinates and junction gaps per slot of every maximal path row, over all reads that collapse
+        onto it (cluster_paths and cluster_path_containment first, the paths made with the same ``qkey``): ``qkey``
+        and ``qend`` (int32, or None = no gaps, the gap columns all 0) per CSR interval.  Returns eleven int32
+        columns of n_tokens each, in the slots' order (``tok_off`` of cluster_paths): ``(n_cov, n_link, start_min,
+        start_med, start_max, end_min, end_med, end_max, gap_min, gap_med, gap_max)``; ``n_cov`` intervals and
+        ``n_link`` read links stand behind a slot, the medians are lower medians, and the slots of rows that are not
+        maximal hold 0."""
+        return self._cluster_collapsed_segments('fslr_cluster_collapsed_segments', qkey, qend)
+
+    def cluster_collapsed_segments_any(self, qkey, qend=None):
+        """cluster_collapsed_segments for a context that holds reads of more than 64 intervals
+        (fslr_cluster_collapsed_segments_any; cluster_paths_any first): ``qkey`` and ``qend`` per interval of the real
+        CSR, in its order.  On a context without such reads it is cluster_collapsed_segments, byte for byte."""
+        return self._cluster_collapsed_segments('fslr_cluster_collapsed_segments_any', qkey, qend)
+
+    def _cluster_collapsed_segments(self, name, qkey, qend):
+        qkey = np.ascontiguousarray(qkey, dtype=np.int32)
+        if qkey.ndim != 1:
+            raise ValueError('qkey must be one-dimensional')
+        if qend is not None:
+            qend = np.ascontiguousarray(qend, dtype=np.int32)
+            if qend.shape != qkey.shape:
+                raise ValueError('qend must have qkey\'s shape')
+        nt = ctypes.c_int64(0)
+        # (an empty array still passes an address: NULL keys are an error of their own)
+        self._check(getattr(self._L, name)(
+            self._h, _ptr(qkey) if qkey.size else _ptr(np.zeros(1, np.int32)),
+            None if qend is None else _ptr(qend) if qend.size else _ptr(np.zeros(1, np.int32)), int(qkey.size), ctypes.byref(nt)))
+        nt = int(nt.value)
+        n_cov, n_link = np.empty(nt, np.int32), np.empty(nt, np.int32)
+        start, end, gap = (np.empty((3, nt), np.int32) for _ in range(3))
+        self._check(self._L.fslr_get_cluster_collapsed_segments(self._h, _ptr(n_cov), _ptr(n_link), _ptr(start), _ptr(end),
+                                                                _ptr(gap), nt))
+        return (n_cov, n_link, start[0], start[1], start[2], end[0], end[1], end[2], gap[0], gap[1], gap[2])
+
+    def cluster_collapsed_segments_timings(self) -> dict:
+        """HIP-event time (ms) of the last cluster_collapsed_segments, uploads excluded (profiling contexts)."""
+        ms = (ctypes.c_float * 1)()
+        self._check(self._L.fslr_cluster_collapsed_segments_timings(self._h, ms))
+        return {'collapsed': float(ms[0])}

@@ -52,7 +52,8 @@ __all__ = ['IntervalItem', 'keep_fillings', 'rename_chromosomes', 'chrom_to_str'
            'calculate_overlap', 'overall_jaccard_similarity', 'different_lengths_or_alignments', 'PairScores',
            'PairMatching',
            'device_coverage', 'DeviceCoverage', 'ClusterTable', 'cluster_table', 'ClusterLoci',
-           'ClusterJunctions', 'ClusterPaths', 'ClusterPathSegments', 'ClusterPathContainment']
+           'ClusterJunctions', 'ClusterPaths', 'ClusterPathSegments', 'ClusterPathContainment',
+           'ClusterCollapsedSegments']
 
 
 class EdgeCapWarning(UserWarning):
@@ -751,6 +752,58 @@ class ClusterPathContainment:
                              'collapsed_reads': self.collapsed_reads})
 
 
+class ClusterCollapsedSegments:
+    """DeviceIntervalIndex.cluster_collapsed_segments' result (fslr_cluster_collapsed_segments): per piece of every
+    MAXIMAL row of ``paths`` (slot ``tok_off[row] + piece``) the minimum, lower median and maximum of the reference
+    start and end of the piece over all reads that collapse onto the row (``containment.collapse_to``), and per link
+    between a piece and the next the same of the query-space gap.  A truncated read counts at the pieces it covers
+    and nowhere else: ``n_cov`` intervals and ``n_link`` read links stand behind a slot.  The slots of rows that are
+    not maximal hold 0 in every column; a row's last piece has ``n_link`` 0 and gap 0, 0, 0; without ``qend`` every
+    gap is 0 and ``n_link`` is still filled.  Eleven int32 columns of ``n_tokens`` each.  ``paths`` is the
+    ClusterPaths and ``containment`` the ClusterPathContainment the call stood on."""
+
+    NAMES = ('n_cov', 'n_link', 'start_min', 'start_med', 'start_max', 'end_min', 'end_med', 'end_max',
+             'gap_min', 'gap_med', 'gap_max')
+    FRAME_COLUMNS = ('cluster', 'path', 'piece', 'chrom', 'start', 'end', 'strand', 'n_cov', 'start_min', 'start_max',
+                     'end_min', 'end_max', 'gap_min', 'gap', 'gap_max', 'n_link', 'collapsed_reads')
+
+    def __init__(self, paths, containment, n_cov, n_link, start_min, start_med, start_max, end_min, end_med, end_max,
+                 gap_min, gap_med, gap_max):
+        self.paths, self.containment = paths, containment
+        self.n_cov, self.n_link = n_cov, n_link
+        self.start_min, self.start_med, self.start_max = start_min, start_med, start_max
+        self.end_min, self.end_med, self.end_max = end_min, end_med, end_max
+        self.gap_min, self.gap_med, self.gap_max = gap_min, gap_med, gap_max
+
+    def __len__(self):
+        return int(self.n_cov.shape[0])
+
+    def columns(self):
+        """The eleven columns in NAMES' order."""
+        return tuple(getattr(self, k) for k in self.NAMES)
+
+    def to_frame(self):
+        """One line per piece of every maximal row (FRAME_COLUMNS): ``cluster, path`` (0-based within its cluster),
+        ``piece`` (0-based within its path), ``chrom`` (of the piece's loci row), ``start, end`` (the medians),
+        ``strand`` ('-' for a reversed piece), ``n_cov``, ``start_min, start_max, end_min, end_max``, ``gap_min, gap,
+        gap_max`` (gap = the median), ``n_link`` and ``collapsed_reads`` of the row."""
+        p, ct = self.paths, self.containment
+        n_pieces = np.diff(p.tok_off)
+        row = np.repeat(np.arange(len(p), dtype=np.int64), n_pieces)
+        piece = np.arange(len(self), dtype=np.int64) - np.repeat(p.tok_off[:-1], n_pieces)
+        keep = np.asarray(ct.collapse_to, np.int64)[row] == row
+        row = row[keep]
+        strand = np.where(p.rev == 0, '+', '-').astype(object)
+        return pd.DataFrame({'cluster': p.cluster_of_row()[row], 'path': p._path_in_cluster()[row], 'piece': piece[keep],
+                             'chrom': np.asarray(p.loci.chrom)[p.locus][keep], 'start': self.start_med[keep],
+                             'end': self.end_med[keep], 'strand': strand[keep], 'n_cov': self.n_cov[keep],
+                             'start_min': self.start_min[keep], 'start_max': self.start_max[keep],
+                             'end_min': self.end_min[keep], 'end_max': self.end_max[keep],
+                             'gap_min': self.gap_min[keep], 'gap': self.gap_med[keep], 'gap_max': self.gap_max[keep],
+                             'n_link': self.n_link[keep],
+                             'collapsed_reads': np.asarray(ct.collapsed_reads, np.int64)[row]})
+
+
 def _rev_bits(strand) -> np.ndarray:
     """uint8 0/1 of a strand column given as booleans, 0/1 or '+' / '-' ('-' and true values are 1)."""
     s = np.asarray(strand)
@@ -1371,6 +1424,40 @@ class DeviceIntervalIndex:
         paths = self.cluster_paths_any(qstart, strand, G_or_labels)
         return ClusterPathContainment(paths, *self.ctx.cluster_path_containment())
 
+    def cluster_collapsed_segments(self, qstart, qend=None, strand=None, G_or_labels=None) -> ClusterCollapsedSegments:
+        """Consensus coordinates and junction gaps per piece of every full-length (maximal) cluster path, taken over
+        all reads that collapse onto it (fslr_cluster_collapsed_segments): cluster_path_segments' statistics with the
+        truncated reads of cluster_path_containment counted at the pieces they cover.  The arguments are
+        cluster_path_segments'; the loci, the paths and the containment are made when needed and the path rows this
+        index made with the same ``qstart`` and ``strand`` since its last table are reused.  An index with reads of
+        more than 64 intervals raises NotImplementedError.  The result holds its ClusterPaths as ``.paths`` and its
+        ClusterPathContainment as ``.containment``."""
+        if self.long is not None:
+            raise NotImplementedError(f'cluster_collapsed_segments does not take an index with reads of more than '
+                                      f'{FSLR_MAX_L} intervals (cluster_collapsed_segments_any does)')
+        return self._collapsed_segments(False, qstart, qend, strand, G_or_labels)
+
+    def cluster_collapsed_segments_any(self, qstart, qend=None, strand=None, G_or_labels=None) -> ClusterCollapsedSegments:
+        """cluster_collapsed_segments for an index that may hold reads of more than 64 intervals, up to 4096
+        (fslr_cluster_collapsed_segments_any); the rules for ``G_or_labels`` are cluster_junctions_any's.  On an index
+        without long reads it returns what cluster_collapsed_segments returns."""
+        return self._collapsed_segments(True, qstart, qend, strand, G_or_labels)
+
+    def _collapsed_segments(self, any_length, qstart, qend, strand, G_or_labels):
+        call = self.ctx.cluster_collapsed_segments_any if any_length else self.ctx.cluster_collapsed_segments
+        n = int(self.csr.n_intervals)
+        qe = None
+        if qend is not None:
+            e = np.asarray(qend)
+            if e.shape != (n,):
+                raise ValueError(f'qend holds {e.shape} values, the data list {n} intervals')
+            if e.dtype.kind not in 'iu' or (e.size and (e.min() < -(1 << 31) or e.max() >= (1 << 31))):
+                raise ValueError('qend must hold int32 values')
+            qe = e[np.asarray(self.csr.data_pos, np.int64)].astype(np.int32)
+        # through cluster_paths_any (resident rows are reused under _paths_to_reuse) and cluster_path_containment
+        ct = self.cluster_path_containment(qstart, strand, G_or_labels)
+        return ClusterCollapsedSegments(ct.paths, ct, *call(self._paths_made[1], qe))
+
     def __getitem__(self, chrom):
         return ChromosomeView(self, chrom)
 
@@ -1532,6 +1619,14 @@ class MultiGpuIndex:
         raise NotImplementedError('a multi-GPU index lives in the rank processes and cannot give path containment '
                                   'from here (fslr_cluster_path_containment needs the path rows on one context); '
                                   'build it with n_gpus=1')
+
+    def cluster_collapsed_segments(self, *args, **kwargs):
+        raise NotImplementedError('a multi-GPU index lives in the rank processes and cannot give collapsed path '
+                                  'segments from here (fslr_cluster_collapsed_segments needs the whole index on one '
+                                  'context); build it with n_gpus=1')
+
+    def cluster_collapsed_segments_any(self, *args, **kwargs):
+        return self.cluster_collapsed_segments(*args, **kwargs)
 
     def cluster_junctions_any(self, *args, **kwargs):
         return self.cluster_junctions(*args, **kwargs)

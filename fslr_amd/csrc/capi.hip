@@ -235,6 +235,7 @@ void fslr_ctx_destroy(fslr_ctx* c) {
   fslr_paths_free(c);
   fslr_segments_free(c);
   fslr_containment_free(c);
+  fslr_collapsed_free(c);
   fslr_match_free(c);
   fslr_append_free(c);
   fslr_remove_free(c);

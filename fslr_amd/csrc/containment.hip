@@ -95,6 +95,15 @@ void dfree(T*& p) {
 
 void fslr_containment_drop(fslr_ctx* c) {
   if (c->ctw) c->ctw->have = false;
+  fslr_collapsed_drop(c);                   // the collapsed segments stand on these rows
+}
+
+bool fslr_containment_view(const fslr_ctx* c, fslr_containment_rows* v) {
+  const ContainmentWork* w = c->ctw;
+  if (!w || !w->have) return false;
+  *v = fslr_containment_rows{w->coff, w->pairs, w->pairs ? w->pairs + w->n_pairs : nullptr, w->prev,
+                             w->rows32 ? w->rows32 + w->n_rows : nullptr, w->n_rows, w->n_pairs};
+  return true;
 }
 
 void fslr_containment_free(fslr_ctx* c) {
@@ -709,6 +718,7 @@ int containment_run(fslr_ctx* c, int64_t* n_pairs_out) {
     w->timed = true;
   }
   // install
+  fslr_collapsed_drop(c);                   // collapsed segments of the rows that go
   std::swap(w->coff, nr.coff);
   std::swap(w->pairs, nr.pairs);
   std::swap(w->prev, nr.prev);

@@ -191,6 +191,7 @@ struct fslr_ctx {
   struct PathWork* ptw = nullptr;        // fslr_cluster_paths' resident rows, its scratch and its last call's time (paths.hip)
   struct SegmentWork* sgw = nullptr;     // fslr_cluster_path_segments' resident rows, its scratch and its last call's time (segments.hip)
   struct ContainmentWork* ctw = nullptr; // fslr_cluster_path_containment's resident rows, its scratch and its last call's time (containment.hip)
+  struct CollapsedWork* csw = nullptr;   // fslr_cluster_collapsed_segments' resident rows, its scratch and its last call's time (collapsed.hip)
   // reads of more than FSLR_MAX_L intervals (long.hip): the virtual-read map and the long-pair stage
   bool lg_set = false;
   // fslr_set_reads_any: virtual interval k is real interval lg_perm[k] (thresholds arrive in the real
@@ -284,6 +285,20 @@ void fslr_segments_drop(fslr_ctx* c);
 // (the path rows they name are dropped or replaced)
 void fslr_containment_free(fslr_ctx* c);
 void fslr_containment_drop(fslr_ctx* c);
+// the resident containment rows for fslr_cluster_collapsed_segments (containment.hip): false without rows; coff
+// [n_rows + 1]; outer, offset, rev [n_pairs] (null without pairs); collapse_to [n_rows]
+struct fslr_containment_rows {
+  const long long* coff;
+  const int *outer, *offset;
+  const unsigned char* rev;
+  const int* collapse_to;
+  int64_t n_rows, n_pairs;
+};
+bool fslr_containment_view(const fslr_ctx* c, fslr_containment_rows* v);
+// frees the collapsed path segments' rows and scratch (collapsed.hip); fslr_collapsed_drop forgets the rows alone
+// (the containment rows or the path rows they stand on are dropped or replaced)
+void fslr_collapsed_free(fslr_ctx* c);
+void fslr_collapsed_drop(fslr_ctx* c);
 // frees the read matching's buffers and its saved batch (match.hip)
 void fslr_match_free(fslr_ctx* c);
 // frees the append's batch scratch and its second set of data-order buffers (append.hip)

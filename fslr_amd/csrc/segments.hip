@@ -29,6 +29,8 @@
 //   k_seg_lds       S < k <= T: one workgroup per (slot, stream), chain.hpp's bitonic sort in LDS
 //   k_seg_select    k > T: one workgroup per (slot, stream), block min / max and an exact radix select, four
 //                   rounds of eight bits with integer LDS counters
+// The chain walk behind k_seg_emit / k_seg_emit_long and the three tier kernels live in segshared.hpp, shared with
+// collapsed.hip; EmitArgs below says what the walk writes per piece here.
 // No block waits for another.  Every bucket word has one writer; a gap word of the output is zeroed and then
 // written at most once; the LDS counters take integer additions whose sum does not depend on the order.  The
 // bytes are the same on every run.
@@ -46,6 +48,7 @@
 #include "fslr_hip.h"
 #include "idxsearch.hpp"
 #include "kernels.hpp"
+#include "segshared.hpp"
 #include "wave.hpp"
 
 using namespace fslr;
@@ -95,8 +98,6 @@ constexpr int kBlock = 256;
 constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int64_t kMaxItems = int64_t(1) << 30;             // hipcub's item count is an int
 constexpr size_t kStageBytes = size_t(4) << 20;
-constexpr int kSmallMax = 64;                               // a lane group is at most a wavefront
-constexpr int kLdsMax = kChainMaxL;                         // chain_sort_lds' words
 
 template <typename T>
 void dfree(T*& p) {
@@ -166,6 +167,14 @@ __global__ __launch_bounds__(kBlock) void k_seg_ord(const unsigned* __restrict__
 }
 
 // ---- emit ---------------------------------------------------------------------------------------
+// a clustered read as the emit kernels see it: len == 0 when it writes nothing
+struct EmitRead {
+  int len = 0, first = 0, k = 0, o = 0, flip = 0;
+  long long t0 = 0, b0 = 0;
+};
+
+// what segshared.hpp's chain walk writes per piece here: the value of (row, position p, ordinal o) into the row's
+// buckets, or straight into the output for a row of one read
 struct EmitArgs {
   RealReads rr;                      // the real lists on a context with virtual reads (n = the real reads)
   const int* longs;                  // [n_long] the reads of k_seg_emit_long
@@ -182,386 +191,76 @@ struct EmitArgs {
   int* slot_k;                       // [nt]
   long long* slot_base;              // [nt]
   unsigned char* slot_last;          // [nt]
+
+  using Read = EmitRead;
+  static constexpr bool kPrevGap = false;
+
+  // read r of `len` intervals (the caller checked it against its kernel's range): its row, ordinal and bucket
+  __device__ __forceinline__ EmitRead read(long long r, int first, int len) const {
+    EmitRead e;
+    e.first = first;
+    const int row = por[r];
+    if (row < 0 || row >= n_rows) return e;
+    e.t0 = tok_off[row];
+    e.k = nreads[row];
+    e.o = ord[r];
+    e.b0 = base[row];
+    e.flip = flipped[r] != 0;
+    // a read's row has the read's length and holds its ordinal, so every slot below lies in the row
+    if (tok_off[row + 1] - e.t0 == len && e.o >= 0 && e.o < e.k) e.len = len;
+    return e;
+  }
+
+  // the interval at chain rank `rank` of read e: record rec, and with link (a next piece exists and the caller
+  // brought the query ends) the gap to that piece
+  __device__ __forceinline__ void piece(const EmitRead& e, int rank, long long, const int4& rec, bool link, int gap, int) const {
+    const int len = e.len, k = e.k, o = e.o;
+    const long long t0 = e.t0, b0 = e.b0;
+    const int p = e.flip ? len - 1 - rank : rank;
+    const long long s = t0 + p;
+    FSLR_BOUND(s, nt);
+    // the link to the next piece of the read's own chain lies between positions p and p -+ 1: stored at the smaller
+    const int pl = e.flip ? len - 2 - rank : rank;
+    if (k == 1) {
+      out[s] = out[nt + s] = out[2 * nt + s] = rec.y;
+      out[3 * nt + s] = out[4 * nt + s] = out[5 * nt + s] = rec.z;
+      if (link) {
+        FSLR_BOUND(t0 + pl, nt);
+        out[6 * nt + t0 + pl] = out[7 * nt + t0 + pl] = out[8 * nt + t0 + pl] = gap;
+      }
+      slot_k[s] = 1;
+    } else {
+      const long long at = b0 + static_cast<long long>(p) * k + o;
+      FSLR_BOUND(at, n_vals);
+      vs[at] = rec.y;
+      ve[at] = rec.z;
+      if (link) {
+        FSLR_BOUND(b0 + static_cast<long long>(pl) * k + o, n_vals);
+        vg[b0 + static_cast<long long>(pl) * k + o] = gap;
+      }
+      if (o == 0) {                                   // one read per row describes its slots
+        slot_k[s] = k;
+        slot_base[s] = b0 + static_cast<long long>(p) * k;
+        slot_last[s] = static_cast<unsigned char>(p == len - 1);
+      }
+    }
+  }
 };
 
-__device__ __forceinline__ int sat32(long long v) {
-  return static_cast<int>(max(static_cast<long long>(INT_MIN), min(static_cast<long long>(INT_MAX), v)));
-}
-
-__device__ __forceinline__ int unbias(unsigned u) { return static_cast<int>(u ^ 0x80000000u); }
-
-// a clustered read as the emit kernels see it: len == 0 when it writes nothing
-struct EmitRead {
-  int len = 0, first = 0, k = 0, o = 0, flip = 0;
-  long long t0 = 0, b0 = 0;
-};
-
-// read r of `len` intervals (the caller checked it against its kernel's range): its row, ordinal and bucket
-__device__ __forceinline__ EmitRead emit_read(const EmitArgs& a, long long r, int first, int len) {
-  EmitRead e;
-  e.first = first;
-  const int row = a.por[r];
-  if (row < 0 || row >= a.n_rows) return e;
-  e.t0 = a.tok_off[row];
-  e.k = a.nreads[row];
-  e.o = a.ord[r];
-  e.b0 = a.base[row];
-  e.flip = a.flipped[r] != 0;
-  // a read's row has the read's length and holds its ordinal, so every slot below lies in the row
-  if (a.tok_off[row + 1] - e.t0 == len && e.o >= 0 && e.o < e.k) e.len = len;
-  return e;
-}
-
-// the interval at chain rank `rank` of read e: record rec, and with link (a next piece exists and the caller
-// brought the query ends) the gap to that piece
-__device__ __forceinline__ void emit_piece(const EmitArgs& a, const EmitRead& e, int rank, const int4& rec, bool link, int gap) {
-  const int len = e.len, k = e.k, o = e.o;
-  const long long t0 = e.t0, b0 = e.b0;
-  const int p = e.flip ? len - 1 - rank : rank;
-  const long long s = t0 + p;
-  FSLR_BOUND(s, a.nt);
-  // the link to the next piece of the read's own chain lies between positions p and p -+ 1: stored at the smaller
-  const int pl = e.flip ? len - 2 - rank : rank;
-  if (k == 1) {
-    a.out[s] = a.out[a.nt + s] = a.out[2 * a.nt + s] = rec.y;
-    a.out[3 * a.nt + s] = a.out[4 * a.nt + s] = a.out[5 * a.nt + s] = rec.z;
-    if (link) {
-      FSLR_BOUND(t0 + pl, a.nt);
-      a.out[6 * a.nt + t0 + pl] = a.out[7 * a.nt + t0 + pl] = a.out[8 * a.nt + t0 + pl] = gap;
-    }
-    a.slot_k[s] = 1;
-  } else {
-    const long long at = b0 + static_cast<long long>(p) * k + o;
-    FSLR_BOUND(at, a.n_vals);
-    a.vs[at] = rec.y;
-    a.ve[at] = rec.z;
-    if (link) {
-      FSLR_BOUND(b0 + static_cast<long long>(pl) * k + o, a.n_vals);
-      a.vg[b0 + static_cast<long long>(pl) * k + o] = gap;
-    }
-    if (o == 0) {                                   // one read per row describes its slots
-      a.slot_k[s] = k;
-      a.slot_base[s] = b0 + static_cast<long long>(p) * k;
-      a.slot_last[s] = static_cast<unsigned char>(p == len - 1);
-    }
-  }
-}
-
-// 64 / W reads side by side: read r (valid: it exists) on the W-lane group of this lane, interval j = the lane's
-// place in the group.  lds: this wavefront's 64 slots.
-template <int W>
-__device__ __forceinline__ void emit_group(const EmitArgs& a, long long r, bool valid, int lane, int* lds) {
-  const int j = lane & (W - 1), gbase = lane & ~(W - 1);
-  EmitRead e;
-  if (valid) {
-    FSLR_BOUND(r, a.n);
-    const int4 rm = a.rr.rmeta[r];
-    const int len = a.rr.len(r, rm);
-    // len > W: a real read of more than FSLR_MAX_L intervals (k_seg_emit_long's; its first chunk is not a read of
-    // its own); otherwise the caller chose W for its reads
-    if (len <= W) e = emit_read(a, r, rm.x, len);
-  }
-  const int len = e.len;
-  const bool have = j < len;
-  int key = 0, qe = 0;
-  int4 rec = make_int4(0, 0, 0, 0);
-  if (have) {
-    const long long i = static_cast<long long>(e.first) + j;
-    FSLR_BOUND(i, a.ni);
-    rec = a.iv[i];
-    key = a.qkey[i];
-    if (a.qend) qe = a.qend[i];
-  }
-  const int rank = chain_rank(key, len, j, gbase);
-  if (have) lds[gbase + rank] = key;                // rank < len <= W: the group's slots
-  wave_lds_sync();
-  if (have) {
-    const bool link = a.qend && rank + 1 < len;
-    int gap = 0;
-    if (link) gap = sat32(static_cast<long long>(lds[gbase + rank + 1]) - static_cast<long long>(qe));
-    emit_piece(a, e, rank, rec, link, gap);
-  }
-  wave_lds_sync();                                  // the next pass writes the slots again
-}
-
+// four reads per wavefront on 16 lanes, or 32 / 64 lanes when one is longer (segshared.hpp emit_waves)
 __global__ __launch_bounds__(kBlock) void k_seg_emit(EmitArgs a) {
   __shared__ int s_slot[kWavesPerBlock][kWave];
-  const int lane = lane_id(), wv = threadIdx.x / kWave;
-  int* lds = s_slot[wv];
-  // a wavefront takes four consecutive reads at a time
-  for (long long q = blockIdx.x * static_cast<long long>(kWavesPerBlock) + wv; q < a.n_quads;
-       q += gridDim.x * static_cast<long long>(kWavesPerBlock)) {
-    const long long r0 = q * 4;
-    const long long r16 = r0 + (lane >> 4);
-    int len = 0;
-    if (r16 < a.n) {
-      FSLR_BOUND(r16, a.n);
-      len = a.rr.len(r16, a.rr.rmeta[r16]);
-      if (a.por[r16] < 0 || len > FSLR_MAX_L) len = 0;
-    }
-    const bool over16 = __ballot(len > 16) != 0ull, over32 = __ballot(len > 32) != 0ull;
-    if (__ballot(len > 0) == 0ull) continue;        // wave-uniform: nothing to write
-    if (!over16) {
-      emit_group<16>(a, r16, r16 < a.n, lane, lds);
-    } else if (!over32) {
-      for (int p = 0; p < 2; ++p) {
-        const long long r = r0 + 2 * p + (lane >> 5);
-        emit_group<32>(a, r, r < a.n, lane, lds);
-      }
-    } else {
-      for (int p = 0; p < 4; ++p) emit_group<64>(a, r0 + p, r0 + p < a.n, lane, lds);
-    }
-  }
+  emit_waves(a, s_slot[threadIdx.x / kWave]);
 }
 
-// One workgroup per clustered read of more than FSLR_MAX_L intervals (a.longs): the chain order by an LDS sort;
-// the thread that holds rank t takes its interval's place in the list from the word's low bits and the next
-// piece's key from word t + 1, and writes what emit_group's lane writes.  32 KiB of LDS, no atomics.
+// one workgroup per clustered read of more than FSLR_MAX_L intervals (segshared.hpp emit_long_blocks); 32 KiB of
+// LDS, no atomics
 __global__ __launch_bounds__(kChainBlock) void k_seg_emit_long(EmitArgs a) {
   __shared__ unsigned long long s_w[kChainMaxL];
-  for (long long q = blockIdx.x; q < a.n_long; q += gridDim.x) {
-    FSLR_BOUND(q, a.n_long);
-    const int r = a.longs[q];
-    FSLR_BOUND(r, a.n);
-    const int4 rm = a.rr.rmeta[r];
-    const int rlen = a.rr.len(r, rm), off2 = a.rr.second(r, rlen);
-    EmitRead e;
-    if (rlen > FSLR_MAX_L && rlen <= kChainMaxL) e = emit_read(a, r, rm.x, rlen);
-    const int len = min(e.len, kChainMaxL);         // bounds the LDS indices below
-    if (len == 0) continue;                         // block-uniform: no barrier is skipped by a part of the block
-    chain_sort_lds(s_w, a.qkey, e.first, off2, len, a.ni);
-    for (int t = threadIdx.x; t < len; t += kChainBlock) {
-      FSLR_BOUND(t, kChainMaxL);
-      const unsigned long long w = s_w[t];
-      const int j = static_cast<int>(w & (kChainMaxL - 1));
-      FSLR_BOUND(j, len);
-      const long long i = list_at(e.first, off2, j);
-      FSLR_BOUND(i, a.ni);
-      const int4 rec = a.iv[i];
-      const bool link = a.qend && t + 1 < len;
-      int gap = 0;
-      if (link) {
-        FSLR_BOUND(t + 1, kChainMaxL);
-        gap = sat32(static_cast<long long>(unbias(static_cast<unsigned>(s_w[t + 1] >> 12))) - static_cast<long long>(a.qend[i]));
-      }
-      emit_piece(a, e, t, rec, link, gap);
-    }
-    __syncthreads();                                // the next read writes the words again
-  }
-}
-
-// ---- tiers --------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void k_seg_flags(const int* __restrict__ slot_k, long long nt, int small, int lds,
-                                                      unsigned char* __restrict__ flag) {
-  for (long long s = blockIdx.x * static_cast<long long>(kBlock) + threadIdx.x; s < nt; s += gridDim.x * static_cast<long long>(kBlock)) {
-    FSLR_BOUND(s, nt);
-    const int k = slot_k[s];
-    flag[s] = k >= 2 && k <= small;
-    flag[nt + s] = k >= 2 && k > small && k <= lds;
-    flag[2 * nt + s] = k >= 2 && k > small && k > lds;
-  }
-}
-
-struct SelArgs {
-  const int* list;                   // [n_list] the tier's slots
-  long long n_list, n_items;         // items: stream * n_list + place in the list
-  const int* slot_k;
-  const long long* slot_base;
-  const unsigned char* slot_last;
-  const int* vals[3];                // start, end, gap buckets
-  long long nt, n_vals;
-  int* out;                          // [9 x nt]
-};
-
-// the k of an item, 0 for none (past the end, or the gap stream of a row's last slot: its words stay 0)
-__device__ __forceinline__ int item_k(const SelArgs& a, long long item, long long* s, int* stream) {
-  if (item >= a.n_items) return 0;
-  const long long i = item % a.n_list;
-  *stream = static_cast<int>(item / a.n_list);
-  FSLR_BOUND(i, a.n_list);
-  *s = a.list[i];
-  FSLR_BOUND(*s, a.nt);
-  if (*stream == 2 && a.slot_last[*s]) return 0;
-  return a.slot_k[*s];
-}
-
-__device__ __forceinline__ void put3(const SelArgs& a, int stream, long long s, int c, int v) {
-  FSLR_BOUND(s, a.nt);
-  a.out[(3 * stream + c) * a.nt + s] = v;
-}
-
-// 64 / W items side by side: lane j of the group holds value j of the item's bucket
-template <int W>
-__device__ __forceinline__ void small_group(const SelArgs& a, long long item, int lane) {
-  const int j = lane & (W - 1), gbase = lane & ~(W - 1);
-  long long s = 0;
-  int stream = 0;
-  int k = item_k(a, item, &s, &stream);
-  if (k > W) k = 0;                                 // the caller chose W for its items
-  const bool have = j < k;
-  int v = 0;
-  if (have) {
-    const long long at = a.slot_base[s] + j;
-    FSLR_BOUND(at, a.n_vals);
-    v = a.vals[stream][at];
-  }
-  int kmax = k;
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) kmax = max(kmax, __shfl_xor(kmax, d));
-  int lt = 0, le = 0;
-  for (int i = 0; i < kmax; ++i) {                  // kmax <= W: gbase + i stays in the group
-    const int o = __shfl(v, gbase + i);
-    lt += (i < k) && o < v;
-    le += (i < k) && o <= v;
-  }
-  // the sorted places [lt, le) hold v: the lowest lane that covers a place writes it
-  const int m = (k - 1) / 2;
-  const unsigned long long gmask = W == 64 ? ~0ull : (1ull << (W & 63)) - 1ull;
-  const unsigned long long b_min = (__ballot(have && lt == 0) >> gbase) & gmask;
-  const unsigned long long b_med = (__ballot(have && lt <= m && m < le) >> gbase) & gmask;
-  const unsigned long long b_max = (__ballot(have && le == k) >> gbase) & gmask;
-  if (have) {
-    if (j == __ffsll(static_cast<long long>(b_min)) - 1) put3(a, stream, s, 0, v);
-    if (j == __ffsll(static_cast<long long>(b_med)) - 1) put3(a, stream, s, 1, v);
-    if (j == __ffsll(static_cast<long long>(b_max)) - 1) put3(a, stream, s, 2, v);
-  }
-}
-
-__global__ __launch_bounds__(kBlock) void k_seg_small(SelArgs a) {
-  const int lane = lane_id(), wv = threadIdx.x / kWave;
-  const long long n_quads = (a.n_items + 3) / 4;
-  for (long long q = blockIdx.x * static_cast<long long>(kWavesPerBlock) + wv; q < n_quads;
-       q += gridDim.x * static_cast<long long>(kWavesPerBlock)) {
-    const long long i0 = q * 4;
-    long long s = 0;
-    int stream = 0;
-    const int k = item_k(a, i0 + (lane >> 4), &s, &stream);
-    const bool over16 = __ballot(k > 16) != 0ull, over32 = __ballot(k > 32) != 0ull;
-    if (__ballot(k > 0) == 0ull) continue;          // wave-uniform
-    if (!over16) {
-      small_group<16>(a, i0 + (lane >> 4), lane);
-    } else if (!over32) {
-      for (int p = 0; p < 2; ++p) small_group<32>(a, i0 + 2 * p + (lane >> 5), lane);
-    } else {
-      for (int p = 0; p < 4; ++p) small_group<64>(a, i0 + p, lane);
-    }
-  }
-}
-
-// One workgroup per (slot, stream) of k <= kLdsMax values: chain_sort_lds' words are (biased value, place), so the
-// sorted words give elements 0, (k - 1) / 2 and k - 1.  32 KiB of LDS.
-__global__ __launch_bounds__(kChainBlock) void k_seg_lds(SelArgs a) {
-  __shared__ unsigned long long s_w[kChainMaxL];
-  for (long long item = blockIdx.x; item < a.n_items; item += gridDim.x) {
-    long long s = 0;
-    int stream = 0;
-    const int k = item_k(a, item, &s, &stream);     // block-uniform
-    if (k < 1 || k > kLdsMax) continue;
-    const long long b = a.slot_base[s];
-    FSLR_BOUND(b + k - 1, a.n_vals);
-    // the bucket as a list of k words from its first: interval i of the list is word i (first 0, the rest from 64)
-    chain_sort_lds(s_w, a.vals[stream] + b, 0, FSLR_MAX_L, k, k);
-    if (threadIdx.x == 0) {
-      put3(a, stream, s, 0, unbias(static_cast<unsigned>(s_w[0] >> 12)));
-      put3(a, stream, s, 1, unbias(static_cast<unsigned>(s_w[(k - 1) / 2] >> 12)));
-      put3(a, stream, s, 2, unbias(static_cast<unsigned>(s_w[k - 1] >> 12)));
-    }
-    __syncthreads();                                // the next item writes the words again
-  }
-}
-
-// One workgroup per (slot, stream) of any k: min and max by a block reduction; the lower median by a radix select
-// on the biased value, most significant byte first: each round counts, among the values that share the prefix
-// found so far, the next byte into 256 LDS counters, and thread 0 walks them to the byte that holds the target
-// place.  Four rounds, each one pass over the bucket.
-__global__ __launch_bounds__(kBlock) void k_seg_select(SelArgs a) {
-  __shared__ int s_hist[256];
-  __shared__ int s_red[2 * kWavesPerBlock];
-  __shared__ unsigned s_prefix;
-  __shared__ int s_target;
-  const int lane = lane_id(), wv = threadIdx.x / kWave;
-  for (long long item = blockIdx.x; item < a.n_items; item += gridDim.x) {
-    long long s = 0;
-    int stream = 0;
-    const int k = item_k(a, item, &s, &stream);     // block-uniform
-    if (k < 1) continue;
-    const long long b = a.slot_base[s];
-    FSLR_BOUND(b + k - 1, a.n_vals);
-    const int* v = a.vals[stream] + b;
-    int lo = INT_MAX, hi = INT_MIN;
-    for (int i = threadIdx.x; i < k; i += kBlock) {
-      lo = min(lo, v[i]);
-      hi = max(hi, v[i]);
-    }
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      lo = min(lo, __shfl_xor(lo, d));
-      hi = max(hi, __shfl_xor(hi, d));
-    }
-    if (lane == 0) {
-      s_red[wv] = lo;
-      s_red[kWavesPerBlock + wv] = hi;
-    }
-    if (threadIdx.x == 0) {
-      s_prefix = 0u;
-      s_target = (k - 1) / 2;
-    }
-    for (int round = 0; round < 4; ++round) {
-      const int shift = 24 - 8 * round;
-      s_hist[threadIdx.x] = 0;                      // kBlock == 256 counters
-      __syncthreads();
-      const unsigned prefix = s_prefix;
-      for (int i = threadIdx.x; i < k; i += kBlock) {
-        const unsigned u = static_cast<unsigned>(v[i]) ^ 0x80000000u;
-        // round > 0: shift + 8 <= 24, the bits above this round's byte
-        if (round == 0 || (u >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&s_hist[(u >> shift) & 255u], 1);
-      }
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        int t = s_target, d = 0;
-        while (d < 255 && t >= s_hist[d]) t -= s_hist[d++];      // the counts sum to more than t: d stops in range
-        s_target = t;
-        s_prefix = prefix | (static_cast<unsigned>(d) << shift);
-      }
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-      lo = s_red[0], hi = s_red[kWavesPerBlock];
-#pragma unroll
-      for (int i = 1; i < kWavesPerBlock; ++i) {
-        lo = min(lo, s_red[i]);
-        hi = max(hi, s_red[kWavesPerBlock + i]);
-      }
-      put3(a, stream, s, 0, lo);
-      put3(a, stream, s, 1, unbias(s_prefix));
-      put3(a, stream, s, 2, hi);
-    }
-    __syncthreads();                                // the next item writes the words again
-  }
+  emit_long_blocks(a, s_w);
 }
 
 // ---- host side ----------------------------------------------------------------------------------
-int bits_for(int64_t n_keys) {                   // bits that hold the keys 0 .. n_keys - 1, at least 1
-  int b = 1;
-  while ((int64_t(1) << b) < n_keys) ++b;
-  return b;
-}
-
-// FSLR_SEGS_SMALL (1..64) and FSLR_SEGS_LDS (from it up to 4096), read per call: the largest k of the lane-group
-// tier and of the LDS tier; the tests set them to move the seams between the tiers
-void tier_caps(int* small, int* lds) {
-  *small = kSmallMax;
-  *lds = kLdsMax;
-  if (const char* e = std::getenv("FSLR_SEGS_SMALL")) {
-    const int v = std::atoi(e);
-    if (v >= 1 && v <= kSmallMax) *small = v;
-  }
-  if (const char* e = std::getenv("FSLR_SEGS_LDS")) {
-    const int v = std::atoi(e);
-    if (v >= *small && v <= kLdsMax) *lds = v;
-  }
-}
-
 int ensure_temp(fslr_ctx* c, SegmentWork* w, size_t bytes) {
   if (bytes <= w->temp_bytes && w->temp) return FSLR_OK;
   dfree(w->temp);
@@ -768,17 +467,9 @@ int segments_run(fslr_ctx* c, const int32_t* iv_qkey, const int32_t* iv_qend, in
       for (int t = 0; t < 3; ++t)
         if (cnt[t] < 0 || cnt[t] > nt) return fail(c, FSLR_ERR_STATE, "fslr_cluster_path_segments: inconsistent counts (internal)");
       const int n_streams = iv_qend ? 3 : 2;
-      for (int t = 0; t < 3; ++t) {                   // a tier launches only when it has slots
-        if (cnt[t] == 0) continue;
-        SelArgs sa{lists + t * w->tcap, cnt[t], cnt[t] * n_streams, slot_k, w->tbuf64, slot_last, {vs, ve, vg}, nt, n_vals, nr.out};
-        if (t == 0)
-          k_seg_small<<<grid_for((sa.n_items + 3) / 4, kWavesPerBlock, 256 * 32), kBlock, 0, st>>>(sa);
-        else if (t == 1)
-          k_seg_lds<<<grid_for(sa.n_items, 1, 256 * 8), kChainBlock, 0, st>>>(sa);
-        else
-          k_seg_select<<<grid_for(sa.n_items, 1, 256 * 8), kBlock, 0, st>>>(sa);
-        HIP_TRY(c, hipGetLastError());
-      }
+      // every stream of a slot holds the row's k values; the gap stream of a row's last slot holds none
+      SelArgs sa{nullptr, 0, 0, {slot_k, slot_k, slot_k}, w->tbuf64, slot_last, {vs, ve, vg}, nt, n_vals, nr.out};
+      HIP_TRY(c, launch_tiers(sa, lists, w->tcap, cnt, n_streams, st));
     }
   }
   if (c->profiling) HIP_TRY(c, hipEventRecord(w->ev[1], st));

@@ -275,6 +275,11 @@ def _run(args, basename, tsv, ints, strs, t, pool, ctx_f, state):
         # the graph's table is made anew: whatever an earlier flag left (or, for long reads, did not make) is replaced
         write_cluster_path_containment(f'{basename}.mappings.cluster_path_containment.bed', f'{basename}.mappings.bed',
                                        trees, g)
+    if args.get('cluster_collapsed_segments'):
+        from .main import write_cluster_collapsed_segments
+        # as above: the graph's table is made anew
+        write_cluster_collapsed_segments(f'{basename}.mappings.cluster_collapsed_segments.bed', f'{basename}.mappings.bed',
+                                         trees, g, cmap)
     t['write'] = time.perf_counter() - t3
     # the device buffers go now (the caller's process would free them at exit anyway)
     t5 = time.perf_counter()

@@ -133,6 +133,11 @@ def assign_clusters(bed_file: pd.DataFrame, G: cluster.ClusterGraph, ctx=None):
                    'truncated views (contiguous sub-chains in either direction), its support with their reads counted, '
                    'the full-length path it collapses to, and the paths that contain it as outer:offset:strand (one '
                    'GPU; any input, reads of more than 64 intervals included)')
+@click.option('--cluster-collapsed-segments', required=False, is_flag=True,
+              help='Also write {name}.mappings.cluster_collapsed_segments.bed: one BED line per piece of every '
+                   'full-length cluster path (one that no other path contains) with its consensus coordinates and '
+                   'junction gaps taken over all reads that collapse onto it, the truncated ones counted at the pieces '
+                   'they cover (n_cov, n_link) (one GPU; any input, reads of more than 64 intervals included)')
 @click.option('--cluster-long-reads', required=False, is_flag=True,
               help='With --cluster-junctions / --cluster-paths: also take inputs that hold reads of more than 64 '
                    'intervals (up to 4096; fslr_cluster_junctions_any / fslr_cluster_paths_any) instead of printing a '
@@ -166,6 +171,8 @@ def pipeline(**args):
         raise click.UsageError('--cluster-path-segments-any needs the whole index on one device: run it with --gpus 1')
     if args.get('cluster_path_containment') and (args.get('gpus') or 1) > 1:
         raise click.UsageError('--cluster-path-containment needs the whole index on one device: run it with --gpus 1')
+    if args.get('cluster_collapsed_segments') and (args.get('gpus') or 1) > 1:
+        raise click.UsageError('--cluster-collapsed-segments needs the whole index on one device: run it with --gpus 1')
     if not os.path.exists(args['out']):
         os.mkdir(args['out'])
     if not args['skip_alignment']:
@@ -372,6 +379,23 @@ def write_cluster_path_containment(path, bed_path, trees, G_or_labels):
     return True
 
 
+COLLAPSED_COLUMNS = ('chrom', 'start', 'end', 'cluster', 'path', 'piece', 'strand', 'n_cov', 'start_min', 'start_max',
+                     'end_min', 'end_max', 'gap_min', 'gap', 'gap_max', 'n_link', 'collapsed_reads')
+
+
+def write_cluster_collapsed_segments(path, bed_path, trees, G_or_labels, chrom_to_num_map):
+    """--cluster-collapsed-segments: one line per piece of every maximal cluster path
+    (cluster.ClusterCollapsedSegments.to_frame) as a tab-separated file with COLLAPSED_COLUMNS: chrom, median start and
+    median end first, so it loads as BED; chromosome names as in the input.  Any input is taken: the call goes through
+    cluster_collapsed_segments_any."""
+    qstart, rev, qend = junction_inputs(bed_path, trees.data.index, with_qend=True)
+    frame = trees.cluster_collapsed_segments_any(qstart, qend, rev, G_or_labels).to_frame()
+    name_of = {v: k for k, v in chrom_to_num_map.items()}
+    frame['chrom'] = [name_of.get(c, c) for c in frame['chrom'].tolist()]      # (--cluster-paths named its rows' loci)
+    frame[list(COLLAPSED_COLUMNS)].to_csv(path, sep='\t', index=False)
+    return True
+
+
 def _cluster_and_write(args, basename, bed_file, tsv, t):
     chromosome_mask = set()
     if args['cluster_mask']:
@@ -454,6 +478,10 @@ def _cluster_and_write(args, basename, bed_file, tsv, t):
         # the graph's table is made anew: whatever an earlier flag left (or, for long reads, did not make) is replaced
         write_cluster_path_containment(f'{basename}.mappings.cluster_path_containment.bed', f'{basename}.mappings.bed',
                                        interval_tree, network)
+    if args.get('cluster_collapsed_segments'):
+        # as above: the graph's table is made anew
+        write_cluster_collapsed_segments(f'{basename}.mappings.cluster_collapsed_segments.bed', f'{basename}.mappings.bed',
+                                         interval_tree, network, chrom_to_num_map)
     t['write'] = time.perf_counter() - t3
     if args.get('timings'):
         st = network.stats

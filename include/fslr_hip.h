@@ -952,6 +952,57 @@ int  fslr_get_cluster_path_containment(fslr_ctx *ctx, int64_t *coff, int32_t *ou
                                        int64_t row_capacity, int64_t pair_capacity);
 int  fslr_cluster_path_containment_timings(fslr_ctx *ctx, float *ms);
 
+/* Collapsed path segments: the consensus coordinates of the full-length paths.  fslr_cluster_path_segments takes
+ * its order statistics over the reads that walk exactly one path row; fslr_cluster_path_containment says which
+ * rows are truncated views of a full-length row (collapse_to).  This call fills, for every MAXIMAL path row
+ * (collapse_to[row] == row), each slot with order statistics over ALL reads that collapse onto the row.  A
+ * truncated read contributes at the slots it covers and nowhere else, so the number of contributing reads
+ * differs from slot to slot and is reported.  On top of the resident path rows of the current table
+ * (fslr_cluster_paths / fslr_cluster_paths_any) AND the resident containment rows of those path rows
+ * (fslr_cluster_path_containment).
+ *   Inputs and chain: those of fslr_cluster_path_segments.  iv_qkey [n_intervals] is the column the paths were
+ *   made with; iv_qend [n_intervals] may be NULL: then the three gap columns are 0 and n_link is still filled.
+ *   The chain order of a read is (key ascending, CSR position ascending on equal keys).
+ *   Where a read lands: read r with row A = path_of_read[r], length a and chain rank t has the canonical position
+ *   p = flipped[r] ? a-1-t : t.  Let B = collapse_to[A].  If B == A then q = p.  Otherwise the pair (A, B) is one
+ *   of coff[A] .. coff[A + 1] (collapse_to is one of the rows that contain A; the outers ascend there); with its
+ *   stored offset o and rev d, q = d ? o + (a-1-p) : o + p.  The interval lands in slot tok_off[B] + q.  The link
+ *   between chain ranks t and t+1 is stored at slot tok_off[B] + min(q_t, q_t+1); its gap is that of
+ *   fslr_cluster_path_segments: the later piece's key minus the earlier piece's iv_qend in the read's own chain
+ *   order, computed in 64 bits and saturated to int32.  Every slot index is checked against the row B, which has
+ *   at least a tokens by containment, so a column that is not the paths' own can never leave the row.
+ *   Outputs per token slot of all path rows (n_tokens is that of the path rows): n_cov (the intervals that land
+ *   in the slot), n_link (the read links stored there), start_min|med|max and end_min|med|max over the n_cov
+ *   intervals' reference start and end, gap_min|med|max over the n_link gaps; each triple is [3 x n_tokens] as in
+ *   fslr_get_cluster_path_segments.  The median is the lower median: element (k - 1) / 2 of the ascending values.
+ *   The slots of rows that are not maximal hold 0 in every column; the last slot of a row has n_link = 0 and gap
+ *   0, 0, 0.  The bytes are the same on every run.
+ *   Decided: a truncated read's outermost pieces count with the coordinates they have.  The piece where a read
+ *   broke off is shorter than the full-length reads' piece there; the median is robust against it, the minimum
+ *   and the maximum widen, and n_cov shows how many reads stand behind a figure.
+ * fslr_cluster_collapsed_segments: computes the rows and keeps them resident (*n_tokens, may be NULL); syncs.
+ *   FSLR_ERR_STATE, named in the message: no resident path rows of this table (fslr_cluster_paths first); no
+ *   resident containment rows of those path rows (fslr_cluster_path_containment first); and the state errors of
+ *   fslr_cluster_path_segments (no reads, an index that cannot be searched, no table, a stale table, no loci).
+ *   FSLR_ERR_INVALID: iv_qkey NULL, n_intervals != the context's, a context with virtual reads (the _any call
+ *   takes it), more than 2^30 intervals.  Rows are allocated apart and swapped in at the end: a failed call
+ *   keeps the previous rows.  A successful fslr_cluster_path_containment drops them, and so does whatever drops
+ *   the containment rows or the path rows; fslr_ctx_destroy frees them.  Nothing else on the context is touched.
+ * fslr_cluster_collapsed_segments_any: the same contract for a context with virtual reads (fslr_set_reads_any):
+ *   the columns arrive in the real CSR's order, real reads have 1..FSLR_MAX_ANY_L intervals, a chunk is never a
+ *   read of its own.  On a context without virtual reads the two calls leave the same bytes.
+ * fslr_get_cluster_collapsed_segments: D2H of the rows (NULL outputs are skipped): n_cov, n_link [n_tokens];
+ *   start, end, gap [3 x n_tokens].  FSLR_ERR_STATE without rows, FSLR_ERR_INVALID when token_capacity <
+ *   n_tokens (nothing is written).
+ * fslr_cluster_collapsed_segments_timings (fslr_set_profiling 1 or 2): HIP-event time (ms[0]) of the last
+ *   call's device work, the uploads of the two columns excluded; FSLR_ERR_STATE when it was not profiled.
+ *   FSLR_SEGS_SMALL and FSLR_SEGS_LDS move the tier seams as they do for fslr_cluster_path_segments; a slot's tier
+ *   comes from n_cov. */
+int  fslr_cluster_collapsed_segments(fslr_ctx *ctx, const int32_t *iv_qkey, const int32_t *iv_qend, int64_t n_intervals, int64_t *n_tokens);
+int  fslr_cluster_collapsed_segments_any(fslr_ctx *ctx, const int32_t *iv_qkey, const int32_t *iv_qend, int64_t n_intervals, int64_t *n_tokens);
+int  fslr_get_cluster_collapsed_segments(fslr_ctx *ctx, int32_t *n_cov, int32_t *n_link, int32_t *start, int32_t *end, int32_t *gap, int64_t token_capacity);
+int  fslr_cluster_collapsed_segments_timings(fslr_ctx *ctx, float *ms);
+
 /* Match reads that are NOT in the uploaded set against the resident index: for a query read Q, given
  * like a row of fslr_reads (its intervals in the order its loop walks them, dense chromosome ids of the
  * uploaded CSR, folded iv_thr, its qlen2 and n_alignments), what the reference's pair loop
